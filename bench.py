@@ -21,9 +21,21 @@ Uncached input: a batch smaller than 1 GiB (C1's 64-MB arena) is measured with t
 rotating over several batches of the same config, so that the Infinity Cache cannot serve one
 launch from the lines of the previous (`config.batches_rotated`).
 
-Correctness gate: rank 0's GPU results are compared word for word with the oracle's on the packets
-the cpu_baseline leg processes (the whole batch when its budget allows); every rank also writes its
-sums in place and verifies them (size-independent property).
+A plain run does what `value` needs and no more: set-up, clock ramp, warm-up, the K timed steps,
+the result line.  `--full` adds, after the timed region, everything else the bench measures and
+checks: per-launch times, the two-stream pass, the measured read ceilings of the roofline, the CPU
+baseline and the correctness gate below (a failed gate exits 3); in a plain line those fields are
+null.  The committed lines under profiles/ and the tests that read those fields are `--full` runs.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32), for
+comparing two builds output for output: the same arguments give the same inputs.  Checksum
+workloads: every packet's result word as its two 16-bit halves (out_lo16, out_hi16).  c5: the first
+64 bytes (every byte NAT or the flush rewrites) of a fixed seeded sample of 65,536 frames, with the
+sample's packet indices (float64).  Ranks above 0 write <name>.rank<r>.npy.
+
+Correctness gate (`--full`): rank 0's GPU results are compared word for word with the oracle's on
+the packets the cpu_baseline leg processes (the whole batch when its budget allows); every rank also
+writes its sums in place and verifies them (size-independent property).
 
 `--workload c5 --preimage`: C5's frames after Java's setters (new addresses and ports, stale sums)
 with the 16-B pre-images of the old values; a step is the egress flush that updates their sums
@@ -31,6 +43,7 @@ from the pre-images (vpcsum_pre_async, RFC 1624, only the headers read).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5] [--strong]
        [--preimage] [--share-gpu]   (more ranks than GPUs: a same-card rehearsal, reported as such)
+       [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -235,6 +248,19 @@ def launch_stats(ms: list[float]) -> dict:
             "last5_mean": round(float(a[-k:].mean()), 5)}
 
 
+DUMP_SAMPLE_FRAMES = 1 << 16   # c5: frames of the dumped sample (64 B each as float32: 16 MB)
+
+
+def dump_outputs(dirname: str, rank: int, arrays: dict) -> None:
+    """--dump-outputs: each array as DIR/<name>.npy in float32 (bytes and 16-bit sums are exact in
+    it; packet indices go out as float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.itemsize > 2 else np.float32)
+        np.save(os.path.join(dirname, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -252,9 +278,17 @@ def main():
     ap.add_argument("--team", type=int, default=0, help="kernel variant id (0 = library default)")
     ap.add_argument("--ramp-ms", type=float, default=3000.0,
                     help="run the step kernel this long before the warm-up (clock ramp; reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: per-launch times, "
+                         "the two-stream pass, read ceilings, CPU baseline, correctness gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=6.0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
 
     import torch   # device_count() does not initialise the GPU on this image
     ndev = torch.cuda.device_count()
@@ -379,6 +413,12 @@ def main():
         if n:
             step(i)
     torch.cuda.synchronize()
+    if pre and n and args.dump_outputs:
+        # every flush applies the pre-images once more, and the ramp's launch count depends on the
+        # clock: the dumped frames are those of a fresh batch after exactly K flushes
+        V.synth(arena, n, stride, 0, synth_id, SEED, first, d, stream=stream)
+        V.compute(arena, d, n, None, None, V.MODE_WRITE, stream=stream)
+        pre_img = prep_pre()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -396,17 +436,29 @@ def main():
     if world > 1:
         dist.barrier()
     kernel_ms = t_beg.elapsed_ms(t_end) / args.steps
-    # per-launch times (spread, warm-up drift) from a second pass of K launches, each between
-    # its own events, after the timed region
-    evs = [V.Event() for _ in range(args.steps + 1)]
-    evs[0].record(stream)
-    for i in range(args.steps):
-        if n:
-            step(i)
-        evs[i + 1].record(stream)
-    torch.cuda.synchronize()
-    per_launch = [evs[i].elapsed_ms(evs[i + 1]) for i in range(args.steps)]
-    # The same K steps with two batches in flight, through the library's pipe (vpcsum_pipe_*: the
+    if args.dump_outputs and n:
+        # what the last timed step left: its batch's result words, or (c5) the rewritten frames
+        if nat:
+            idx = np.sort(np.random.default_rng(SEED).choice(n, min(n, DUMP_SAMPLE_FRAMES), replace=False))
+            head = arena.view(n, stride)[torch.from_numpy(idx).cuda(), :64]
+            dump_outputs(args.dump_outputs, rank, {"frames_head64": head.cpu().numpy(), "sample_index": idx})
+        else:
+            words = out[:n].cpu().numpy().view(np.uint32)
+            dump_outputs(args.dump_outputs, rank, {"out_lo16": (words & 0xFFFF).astype(np.uint16),
+                                                   "out_hi16": (words >> 16).astype(np.uint16)})
+    # --full: per-launch times (spread, warm-up drift) from a second pass of K launches, each
+    # between its own events, after the timed region
+    per_launch = None
+    if full:
+        evs = [V.Event() for _ in range(args.steps + 1)]
+        evs[0].record(stream)
+        for i in range(args.steps):
+            if n:
+                step(i)
+            evs[i + 1].record(stream)
+        torch.cuda.synchronize()
+        per_launch = [evs[i].elapsed_ms(evs[i + 1]) for i in range(args.steps)]
+    # --full: the same K steps with two batches in flight, through the library's pipe (vpcsum_pipe_*: the
     # launches alternate between the pipe's two streams, forked from the kernel's stream and joined
     # back into it; each batch with its own out words), so that one launch's ramp and drain overlap
     # its neighbour's -- the rate of a caller that keeps two batches in flight, as the host contexts
@@ -414,7 +466,7 @@ def main():
     # alone, and overlapped launches have no duration of their own.
     peak_main = int(torch.cuda.max_memory_allocated())   # before the second batch below
     pipe_wall, pipe_bytes = 0.0, 0.0
-    if not nat:
+    if full and not nat:
         if n:
             if nb >= 2:   # the rotation's batches, as in the timed region
                 pb = [(arenas[b], ds[b], batch_bytes[b]) for b in range(nb)]
@@ -461,15 +513,16 @@ def main():
     # bytes of the K timed launches (the rotation's batches differ slightly in C3's mix)
     timed_bytes = sum(batch_bytes[i % nb] for i in range(args.steps)) if not nat else bytes_per_step * args.steps
     total_bytes_step = sum_over_ranks(float(timed_bytes)) / args.steps
-    if not nat and n and nb > 1:   # `out` must hold batch 0 for the correctness gate
+    if full and not nat and n and nb > 1:   # `out` must hold batch 0 for the correctness gate
         V.compute(arena, d, n, out, None, V.MODE_COMPUTE, args.team, stream=stream)
         torch.cuda.synchronize()
 
-    # measured read ceilings (context for the roofline fraction)
-    sink = torch.zeros(8192, dtype=torch.int32, device="cuda")
-    e0, e1 = V.Event(), V.Event()
+    # --full: measured read ceilings (context for the roofline fraction)
     read_ceiling = read_bpc = pattern_ceiling = unit_order_ceiling = launch_read = None
-    if not nat and n:
+    if full:
+        sink = torch.zeros(8192, dtype=torch.int32, device="cuda")
+        e0, e1 = V.Event(), V.Event()
+    if full and not nat and n:
         # a reference, not a ceiling: a contiguous streaming read of the whole rotation's arena
         # (every byte, where K2 reads 1504 of every 2048), best of four grids
         span = arena_all[int(desc_np["l3_off"].min()) // 16 * 16:]   # every batch of the rotation
@@ -539,7 +592,7 @@ def main():
             if best is not None:
                 launch_read = {"bytes_per_launch": slab, "ms_per_launch": round(best[0], 5),
                                "workgroups_per_cu": best[1], "GBps": round(slab / (best[0] * 1e-3) / 1e9, 1)}
-    elif nat and n:
+    elif full and nat and n:
         # NAT's own memory operations with no rewrite (vpcsum_nat4_pattern_probe_async: descriptor
         # and entry reads, the header window loads, the one store of [L3+10, checksum end)),
         # priced in the same 72 algorithmic B/packet as `achieved`; --preimage: the pre-image
@@ -563,7 +616,7 @@ def main():
     # every line carries the CPU baseline, N > 1 included: rank 0 times it after the timed region
     # (the other ranks wait at the next collective), on rank 0's first packets
     cpu, gate = None, {}
-    if pre and n:
+    if full and pre and n:
         # the timed flushes applied the pre-images again and again: every rank's gate takes a fresh
         # batch through one flush (then the descriptors lose F_PRE, for the verify below)
         V.synth(arena, n, stride, 0, synth_id, SEED, first, d, stream=stream)
@@ -572,36 +625,34 @@ def main():
         V.pre(arena, d, pre_img, n, None, None, V.MODE_WRITE, V.PRE_FMT_PRE4, stream=stream)
         torch.cuda.synchronize()
         d.view(n, 16)[:, 14] &= 0xFF ^ V.F_PRE
-    if rank == 0 and not args.no_cpu_baseline and not nat and n:
+    want_cpu = full and rank == 0 and not args.no_cpu_baseline
+    if want_cpu and not nat and n:
         cpu, (m, want_out, want_st) = cpu_baseline(args.workload, synth_id, stride, first, args.cpu_budget)
         m = min(m, n)
         got = out[:m].cpu().numpy().view(np.uint32)
         gate["oracle_packets"] = int(m)
         gate["oracle_equal"] = bool(np.array_equal(got, want_out[:m]))
-    elif rank == 0 and not args.no_cpu_baseline and nat and n:
+    elif want_cpu and nat and n:
         cpu, (m, a0, d0, want) = cpu_baseline_nat(rw_np, args.cpu_budget)   # rank 0: first == 0
         got = arena[:m * stride].cpu().numpy()
         gate["oracle_packets"] = int(m)
         gate["oracle_equal"] = bool(np.array_equal(got, want))
-    if not nat and n:
+    if full and not nat and n:
         gate.update(oracle_sample_gate(synth_id, stride, first, out[:n].cpu().numpy().view(np.uint32)))
-    if nat:
-        ok = True
-        if n:
-            V.compute(arena, d, n, None, status, V.MODE_VERIFY, stream=stream)
-            torch.cuda.synchronize()
-            st = status[:n].cpu().numpy()
-            v4 = desc_np["l3_ver"] == 4
-            ok = bool(np.all((st[v4] & 3) == 3))
-    else:
-        ok = True
-        if n:
-            V.compute(arena, d, n, out, status, V.MODE_WRITE, args.team, stream=stream)
-            V.compute(arena, d, n, None, status, V.MODE_VERIFY, args.team, stream=stream)
-            torch.cuda.synchronize()
-            st = status[:n].cpu().numpy()
-            want_ok = np.where(desc_np["flags"] & 1, 1, 0) | np.where(desc_np["flags"] & 2, 2, 0)
-            ok = bool(np.all((st & 3) == want_ok))
+    ok = True
+    if full and nat and n:
+        V.compute(arena, d, n, None, status, V.MODE_VERIFY, stream=stream)
+        torch.cuda.synchronize()
+        st = status[:n].cpu().numpy()
+        v4 = desc_np["l3_ver"] == 4
+        ok = bool(np.all((st[v4] & 3) == 3))
+    elif full and n:
+        V.compute(arena, d, n, out, status, V.MODE_WRITE, args.team, stream=stream)
+        V.compute(arena, d, n, None, status, V.MODE_VERIFY, args.team, stream=stream)
+        torch.cuda.synchronize()
+        st = status[:n].cpu().numpy()
+        want_ok = np.where(desc_np["flags"] & 1, 1, 0) | np.where(desc_np["flags"] & 2, 2, 0)
+        ok = bool(np.all((st & 3) == want_ok))
     ok = ok and gate.get("oracle_equal", True) and gate.get("sample_equal", True)
     all_ok = all_ranks_ok(ok)
 
@@ -626,6 +677,7 @@ def main():
             "vs_baseline": None,
             "dtype": "u8",
             "data": "synthetic",
+            "full": full,
             "config": {
                 "workload": desc_text + (" (one global batch, byte-balanced shards)" if strong else " per GPU"),
                 "global_batch": n_cfg if strong else n_cfg * world,
@@ -634,12 +686,12 @@ def main():
                 "algorithmic_bytes_per_step_rank0": bytes_per_step,
                 "algorithmic_bytes_per_step_all_ranks": int(total_bytes_step),
                 "parallelism": f"shard-per-GPU x{world} (independent streams, no collective)",
-                "verify_all_packets": all_ok,
+                "verify_all_packets": all_ok if full else None,   # checked by --full alone
                 "oracle_gate": gate or None,
                 "batches_rotated": nb,
                 "ramp_ms": round(ramp_ms, 1),
                 "ramp_launches": ramp_launches,
-                "per_launch_ms_rank0": launch_stats(per_launch) if n else None,
+                "per_launch_ms_rank0": launch_stats(per_launch) if n and per_launch else None,
                 "devices_distinct": len({r["device_id"] for r in ranks_info}),
                 "shared_gpu_rehearsal": len({r["device_id"] for r in ranks_info}) < world,
                 "kernel_ms_over_ranks": {"min": min(r["kernel_ms"] for r in ranks_info),

@@ -63,3 +63,18 @@ def test_source_hash_covers_the_library_sources():
     assert len(h) == 16 and h == source_hash()
     # a change to any source changes the hash
     assert source_hash(lambda p: b"x" if p.endswith("nat.hip") else open(os.path.join(REPO, p), "rb").read()) != h
+
+
+def test_dump_outputs_writes_exact_float_arrays(tmp_path):
+    """--dump-outputs: 16-bit sums and bytes are exact in float32, packet indices in float64; a rank
+    above 0 writes under its own name."""
+    import numpy as np
+    sums = np.array([0, 1, 0xFFFF, 0x8001], np.uint16)
+    idx = np.array([0, 9_999_999], np.int64)
+    bench.dump_outputs(str(tmp_path / "d"), 0, {"out_lo16": sums, "sample_index": idx})
+    bench.dump_outputs(str(tmp_path / "d"), 1, {"out_lo16": sums})
+    assert sorted(os.listdir(tmp_path / "d")) == ["out_lo16.npy", "out_lo16.rank1.npy", "sample_index.npy"]
+    got = np.load(tmp_path / "d" / "out_lo16.npy")
+    assert got.dtype == np.float32 and np.array_equal(got.astype(np.uint16), sums)
+    got = np.load(tmp_path / "d" / "sample_index.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), idx)

@@ -19,7 +19,7 @@ def _bench(*args):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--ramp-ms", "0", "--no-cpu-baseline", "--share-gpu"] + list(args)
+           "--ramp-ms", "0", "--full", "--no-cpu-baseline", "--share-gpu"] + list(args)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=REPO)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -71,7 +71,7 @@ def test_bench_two_ranks_strong_shards_per_rank_with_cpu_baseline():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--ramp-ms", "0", "--share-gpu", "--workload", "c4", "--strong", "--cpu-budget", "0.3"]
+           "--ramp-ms", "0", "--full", "--share-gpu", "--workload", "c4", "--strong", "--cpu-budget", "0.3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=REPO)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -9,6 +9,6 @@ run() { local name=$1 lim=$2; shift 2; echo "=== $name $(date +%T)"; timeout -k 
 run c1_ab 400 python tools/cold_ab.py --workload c1 --teams "$V1" --batches 16 --rounds 4
 run c3_ab 400 python tools/cold_ab.py --workload c3 --teams "$V3" --batches 2 --rounds 3
 run c2_ab 400 python tools/cold_ab.py --workload c2 --teams "$V3" --batches 2 --rounds 3
-run bench_c1 300 python bench.py --workload c1 --steps 200 --warmup 20
-run bench_c2 300 python bench.py --steps 200 --warmup 20
+run bench_c1 300 python bench.py --full --workload c1 --steps 200 --warmup 20
+run bench_c2 300 python bench.py --full --steps 200 --warmup 20
 echo ALLDONE

@@ -25,15 +25,15 @@ if has smoke; then
   step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if has benchc2; then
-  step bench_c2 300 python bench.py --steps 200 --warmup 20
-  step bench_c5 400 python bench.py --workload c5 --steps 50 --warmup 5
+  step bench_c2 300 python bench.py --full --steps 200 --warmup 20
+  step bench_c5 400 python bench.py --full --workload c5 --steps 50 --warmup 5
 fi
 if has bench; then
-  step bench_c2 300 python bench.py --steps 200 --warmup 20
-  for w in c1 c3 c4; do step bench_$w 300 python bench.py --workload $w --steps 200 --warmup 20; done
-  step bench_c4_strong 300 python bench.py --workload c4 --strong --steps 200 --warmup 20 --no-cpu-baseline
-  step bench_c5 400 python bench.py --workload c5 --steps 50 --warmup 5
-  step bench_c5pre 400 python bench.py --workload c5 --preimage --steps 50 --warmup 5
+  step bench_c2 300 python bench.py --full --steps 200 --warmup 20
+  for w in c1 c3 c4; do step bench_$w 300 python bench.py --full --workload $w --steps 200 --warmup 20; done
+  step bench_c4_strong 300 python bench.py --full --workload c4 --strong --steps 200 --warmup 20 --no-cpu-baseline
+  step bench_c5 400 python bench.py --full --workload c5 --steps 50 --warmup 5
+  step bench_c5pre 400 python bench.py --full --workload c5 --preimage --steps 50 --warmup 5
 fi
 if has trace; then
   step trace_c2 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_trace -o run -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline
@@ -68,7 +68,7 @@ if has pmc || has pmcpre; then   # the pre-image egress flush on C5 (bench --pre
   step trace_c5pre 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_trace_c5pre -o run -- python3 bench.py --workload c5 --preimage --steps 50 --warmup 5 --no-cpu-baseline
 fi
 if has benchpre; then
-  step bench_c5pre 400 python bench.py --workload c5 --preimage --steps 50 --warmup 5
+  step bench_c5pre 400 python bench.py --full --workload c5 --preimage --steps 50 --warmup 5
 fi
 if has pmc32; then   # last: a counter this gfx950 image may not have
   step pmc_nat15_p32 120 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_sum --output-format csv -d gpurun_out/${TAG}_pmc_nat15 -o p32 -- python3 tools/prof_one.py --nat 0 --nat-mask 15
@@ -80,8 +80,8 @@ if has flush; then   # tools/flush_latency is built in-tree beforehand (g++ line
   step flush 300 ./tools/flush_latency 2000
 fi
 if has rank8; then   # 8 ranks on one card: the strong shards per rank, a functional rehearsal
-  step bench_c4s_8rank 600 python bench.py --workload c4 --strong --gpus 8 --steps 50 --warmup 5 --share-gpu --ramp-ms 300
-  step bench_c5_8rank 600 python bench.py --workload c5 --gpus 8 --steps 20 --warmup 3 --share-gpu --ramp-ms 300
+  step bench_c4s_8rank 600 python bench.py --full --workload c4 --strong --gpus 8 --steps 50 --warmup 5 --share-gpu --ramp-ms 300
+  step bench_c5_8rank 600 python bench.py --full --workload c5 --gpus 8 --steps 20 --warmup 3 --share-gpu --ramp-ms 300
 fi
 if has pmcmode; then   # compute vs verify counters of the default kernel (PMC_CFGS, default c1)
   M="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAVES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES|FETCH_SIZE|WRITE_SIZE|SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM_WR SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
@@ -100,8 +100,8 @@ if has ab; then   # this tree's library against vproxy_amd/libvpcsum_ab.so, unca
   step ab 1100 bash tools/ab_libs_cold.sh ${TAG}_ab "${AB_WS:-c1 c3 c2}" ${AB_ROUNDS:-2} "${AB_MODES:-0 1}"
 fi
 if has rank2; then   # the multi-rank path rehearsed on one GPU (bench.py launches its own ranks)
-  step bench_c2_2rank 300 python bench.py --gpus 2 --steps 50 --warmup 5 --no-cpu-baseline --share-gpu
-  step bench_c5_2rank 400 python bench.py --workload c5 --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --share-gpu
+  step bench_c2_2rank 300 python bench.py --full --gpus 2 --steps 50 --warmup 5 --no-cpu-baseline --share-gpu
+  step bench_c5_2rank 400 python bench.py --full --workload c5 --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --share-gpu
 fi
 if has preflush; then   # the NAT'd 1024-frame host flush, pre-image vs full recompute
   step preflush 300 python tools/preflush.py
