@@ -1383,6 +1383,93 @@ def test_unregister_with_batch_in_flight(V, orc, service):
     ctx.close()
 
 
+def _batch_kinds_inputs(orc, n):
+    """One batch of every kind the context takes, n packets each: Ethernet frames for a registered
+    arena, and pageable arenas with descriptors (one of them outside its arena) for NAT, a
+    MODE_WRITE submit and a pre-image submit."""
+    import egressvec as EV
+    from test_gpu_pre import nat_case
+    rng = np.random.default_rng(1000 + n)
+    fs = EV.frames()
+    R, offs = EV.layout(fs)
+    pick = list(range(0, len(fs), len(fs) // n))[:n]
+    r_desc = EV.oracle_descriptors([fs[i] for i in pick], [offs[i] for i in pick],
+                                   [EV.want_flags(fs[i]["ver"], fs[i]["proto"], i) for i in pick])
+    nat_arena, nat_desc, nat_rw = _nat48_batch(orc, rng, n, 14)
+    wr_arena, wr_desc = orc.synth(n, 2048, 14, O.SYNTH_C3, O.SEED, 4242)
+    pre_arena, pre_desc, pre, _, _ = nat_case(orc, rng, n, O.SYNTH_FUZZ, pad=14)
+    assert np.any(pre_desc["flags"] & O.F_PRE)   # else it would be a plain submit
+    inp = dict(n=n, R=R, fo=np.array([offs[i] for i in pick], np.uint64),
+               fl=np.array([len(fs[i]["frame"]) for i in pick], np.uint32), r_desc=r_desc,
+               nat_arena=nat_arena, nat_desc=nat_desc.copy(), nat_rw=nat_rw, wr_arena=wr_arena, wr_desc=wr_desc.copy(),
+               pre_arena=pre_arena, pre_desc=pre_desc.copy(), pre=pre)
+    for k, arena in (("r_desc", "R"), ("nat_desc", "nat_arena"), ("wr_desc", "wr_arena"), ("pre_desc", "pre_arena")):
+        inp[k]["l3_off"][n // 2] = inp[arena].nbytes + 1
+    return inp
+
+
+def _run_batch_kinds(V, inp, service, waited):
+    """The six submits of test_slots_carry_nothing_between_batch_kinds on a context of their own;
+    waited: each one waited at once.  Returns every result array and every arena."""
+    import ctypes
+    L, n = V.lib(), inp["n"]
+    a = {k: inp[k].copy() for k in ("R", "nat_arena", "wr_arena", "pre_arena")}
+    r = dict(nat_st=np.zeros(n, np.uint8), wr_out=np.zeros(n, np.uint32), wr_st=np.zeros(n, np.uint8),
+             p_desc=np.zeros(n, V.DESC_DTYPE), p_st=np.zeros(n, np.uint8), p_tu=np.zeros(n, V.TUPLE_DTYPE),
+             h_st=np.zeros(n, np.uint8), h_hs=np.zeros(n, V.HSUM_DTYPE), pre_out=np.zeros(n, np.uint32),
+             pre_st=np.zeros(n, np.uint8), v_out=np.zeros(n, np.uint32), v_st=np.zeros(n, np.uint8))
+    ctx = V.Context(0, max_arena=1 << 20, max_pkts=64)
+    ctx.register(a["R"])
+    if service:
+        ctx.set_service(service)
+    tickets = []
+
+    def step(t):
+        tickets.append(t)
+        if waited:
+            ctx.wait(t)
+
+    def frames_call(fn, *results):
+        t = ctypes.c_uint64()
+        rc = fn(ctx.h, a["R"].ctypes.data, a["R"].nbytes, inp["fo"].ctypes.data, inp["fl"].ctypes.data, n,
+                *[None if x is None else x.ctypes.data for x in results], ctypes.byref(t))
+        assert rc == 0, L.vpcsum_last_error()
+        step(t.value)
+
+    step(ctx.nat_submit(a["nat_arena"], inp["nat_desc"], inp["nat_rw"], r["nat_st"], V.NAT_STRICT_JAVA))
+    step(ctx.submit(a["wr_arena"], inp["wr_desc"], r["wr_out"], r["wr_st"], O.MODE_WRITE))
+    frames_call(L.vpcsum_ctx_parse_frames, r["p_desc"], r["p_st"], r["p_tu"])     # finishes the NAT batch
+    frames_call(L.vpcsum_ctx_verify_frames_hsum, None, r["h_st"], r["h_hs"])      # finishes the write-back
+    step(ctx.submit_pre(a["pre_arena"], inp["pre_desc"], inp["pre"], r["pre_out"], r["pre_st"], O.MODE_WRITE))
+    step(ctx.submit(a["R"], inp["r_desc"], r["v_out"], r["v_st"], O.MODE_VERIFY))
+    for t in reversed(tickets):   # all but the last two are completed already
+        ctx.wait(t)
+    ctx.close()
+    r.update(a)
+    return r
+
+
+@pytest.mark.parametrize("service", [0, 20000])
+def test_slots_carry_nothing_between_batch_kinds(V, orc, service):
+    """Batches of different kinds follow each other on the context's two slots without a wait in
+    between -- NAT (staged, strict Java), submit (staged, MODE_WRITE), parse_frames,
+    verify_frames_hsum, submit_pre (staged), submit (zero-copy verify) -- so that each slot goes
+    from one kind to the next, the staged NAT and MODE_WRITE batches finished by the submit that
+    takes their slot, and the tickets are waited in reverse order.  Every result array and every
+    arena equals what a twin context gives with each call waited at once (each of those forms is
+    pinned to the oracle by the tests of its own): nothing of a slot's previous batch -- service
+    sequence, header-sum, descriptor or tuple destination, write-back -- acts on the next."""
+    for n in (5, 37):   # above the 3 inline descriptors, below the service grid's 512
+        inp = _batch_kinds_inputs(orc, n)
+        want = _run_batch_kinds(V, inp, service, waited=True)
+        got = _run_batch_kinds(V, inp, service, waited=False)
+        for k in want:
+            assert got[k].tobytes() == want[k].tobytes(), (n, k)
+        assert not np.array_equal(want["nat_arena"], inp["nat_arena"])   # the batches did act
+        assert not np.array_equal(want["wr_arena"], inp["wr_arena"])
+        assert np.any(want["p_desc"]["l3_len"]) and np.any(want["h_hs"].view(np.uint8)) and np.any(want["v_st"])
+
+
 def test_egress_small_flush_hand_back(V, orc):
     """GpuCsumBatch's SMALL_FLUSH rule in the mirror: a flush below the threshold goes back to the
     native path untouched (no GPU submit); from the threshold on it is computed on the GPU."""

@@ -92,6 +92,18 @@ def test_pni_env_layout_and_errno(libpath, tmp_path):
     assert r.returncode == 0 and "pni layout ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_batch_plan_under_sanitizers(tmp_path):
+    """The host arithmetic of the context's batch path (vproxy_amd/csrc/batch_plan.h: span, 16-B
+    block gather, header extents) in a stand-alone program under ASan / UBSan, every buffer at its
+    exact size (tests/cpp/batch_plan_test.cpp); nothing of the library is linked."""
+    exe = tmp_path / "batch_plan_test"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "vproxy_amd", "csrc"),
+                           os.path.join(REPO, "tests", "cpp", "batch_plan_test.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "batch_plan ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
 def test_survey_entry_points_refuse_before_init(libpath):
     """SURVEY.md §8(b)'s names (vpcsum_init / vpcsum_batch_submit / vpcsum_batch_wait /
     vpcsum_nat_submit) work over one process-wide group; before vpcsum_init every one of them

@@ -135,9 +135,9 @@ int main(int argc, char** argv) {
             }
         }
     }
-    // A small flush right after a large (launched) one, through the service: the large batch stops
-    // the resident grid (api.cpp svc_quiesce), so the small one pays a grid launch.  32 frames after
-    // 1,024 each time, median / p99 of the small flushes.
+    // A small flush right after a large (launched) one, through the service: the grid stays resident
+    // beside the launched batch, so the small one pays no grid launch.  32 frames after 1,024 each
+    // time, median / p99 of the small flushes.
     std::vector<double> alt;
     if (vpcsum_ctx_set_service(ctx, 200000)) {
         fprintf(stderr, "service: %s\n", vpcsum_last_error());

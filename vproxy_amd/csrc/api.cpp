@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_plan.h"
 #include "internal.h"
 #include "vpcsum.h"
 
@@ -102,47 +103,65 @@ int num_cus(int device) {
     return cache[device];
 }
 
-// Per-slot staging of one in-flight batch of a context.
-struct Slot {
-    uint8_t* d_arena = nullptr;
-    vpcsum_desc_t* d_desc = nullptr;
-    uint32_t* d_out = nullptr;
-    uint8_t* d_status = nullptr;
-    vpcsum_desc_t* h_desc = nullptr;   // pinned staging
-    uint32_t* h_out = nullptr;         // pinned staging
-    uint8_t* h_status = nullptr;       // pinned staging
-    uint8_t* h_arena = nullptr;        // pinned staging for unregistered arenas
-    vpcsum_desc_t* dh_desc = nullptr;  // device-side addresses of the pinned staging
-    uint32_t* dh_out = nullptr;
-    uint8_t* dh_status = nullptr;
-    uint64_t* h_foff = nullptr;        // pinned staging of received-frame offsets / lengths
-    uint32_t* h_flen = nullptr;
-    uint64_t* dh_foff = nullptr;
-    uint32_t* dh_flen = nullptr;
-    vpcsum_nat_t* h_rw = nullptr;      // NAT rewrite tables: pinned staging (mapped) and device copy,
-    vpcsum_nat_t* dh_rw = nullptr;     // allocated with the context's first NAT batch
-    vpcsum_nat_t* d_rw = nullptr;
-    vpcsum_tuple_t* h_tu = nullptr;    // flow tuples of a parse batch: pinned (mapped), allocated
-    vpcsum_tuple_t* dh_tu = nullptr;   // with the context's first parse batch
-    vpcsum_hsum_t* h_hs = nullptr;     // ingress header sums of a verify batch: pinned (mapped),
-    vpcsum_hsum_t* dh_hs = nullptr;    // allocated with the context's first such batch
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    int kind = 0;                      // current batch: 0 checksums, 1 NAT rewrite, 2 parse
-    bool zero_copy = false;            // current batch ran on the host frames in place
-    uint32_t svc_seq = 0;              // != 0: the batch went to the low-latency service
-    // the batch currently owned by this slot
+// A pinned host buffer the device reads and writes in place (mapped, coherent: uncached on the
+// GPU): the host pointer and its device address as one value.  alloc() pins and maps; the context
+// and the service pin a group of buffers before they map them, with pin() and map().
+template <class T>
+struct Mapped {
+    T* p = nullptr;     // host
+    T* dev = nullptr;   // the same bytes as the device addresses them
+    hipError_t pin(size_t bytes) { return hipHostMalloc((void**)&p, bytes, hipHostMallocMapped | hipHostMallocCoherent); }
+    hipError_t map() { return hipHostGetDevicePointer((void**)&dev, p, 0); }
+    hipError_t alloc(size_t bytes) {
+        hipError_t e = pin(bytes);
+        if (e == hipSuccess) e = map();
+        if (e != hipSuccess) free();
+        return e;
+    }
+    void free() {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
+    }
+};
+
+// The batch a slot owns from its submit to the wait (or the later submit) that finishes it.
+enum class BatchKind { Csum, Nat, Parse };
+struct Batch {
+    BatchKind kind = BatchKind::Csum;
+    bool zero_copy = false;            // ran on the host frames in place
+    uint32_t svc_seq = 0;              // != 0: went to the low-latency service (no event to wait for)
     uint64_t ticket = 0;
-    bool busy = false;
     uint32_t n = 0;
     uint32_t mode = 0;
-    uint8_t* user_arena = nullptr;
+    uint8_t* user_arena = nullptr;             // staged batch: the frames the results go back into
     const vpcsum_desc_t* user_desc = nullptr;
     uint32_t* user_out = nullptr;
     uint8_t* user_status = nullptr;
     vpcsum_desc_t* user_desc_out = nullptr;   // parse batch: where descriptors and tuples go
     vpcsum_tuple_t* user_tuples = nullptr;
     vpcsum_hsum_t* user_hsum = nullptr;       // verify batch with header sums: where they go
+};
+
+// Per-slot staging of one in-flight batch of a context.
+struct Slot {
+    uint8_t* d_arena = nullptr;
+    vpcsum_desc_t* d_desc = nullptr;
+    uint32_t* d_out = nullptr;
+    uint8_t* d_status = nullptr;
+    Mapped<vpcsum_desc_t> h_desc;      // pinned staging
+    Mapped<uint32_t> h_out;
+    Mapped<uint8_t> h_status;
+    uint8_t* h_arena = nullptr;        // pinned staging for unregistered arenas (not mapped)
+    Mapped<uint64_t> h_foff;           // received-frame offsets / lengths
+    Mapped<uint32_t> h_flen;
+    Mapped<vpcsum_nat_t> h_rw;         // NAT rewrite tables, and their device copy: allocated with the
+    vpcsum_nat_t* d_rw = nullptr;      // context's first NAT batch
+    Mapped<vpcsum_tuple_t> h_tu;       // flow tuples of a parse batch: with the context's first parse batch
+    Mapped<vpcsum_hsum_t> h_hs;        // ingress header sums of a verify batch: with the first such batch
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    bool busy = false;                 // `batch` is in flight
+    Batch batch;
 };
 
 }  // namespace vpcsum
@@ -241,31 +260,24 @@ static_assert(kSvcAuxBytes >= (size_t)vpcsum::kSvcBatchMax * sizeof(vpcsum_pre_t
 
 // Low-latency service of a context (kernels.hip k_csum_service).
 struct Service {
-    vpcsum::SvcMailbox* mb = nullptr;    // host-pinned, coherent (uncached on the GPU), mapped
-    vpcsum::SvcMailbox* dmb = nullptr;   // its device address
+    vpcsum::Mapped<vpcsum::SvcMailbox> mb;   // host-pinned, coherent (uncached on the GPU), mapped
     uint32_t* ctr = nullptr;             // device: workgroups finished with the current batch,
                                          // then (8-B aligned, ctr + 2) the command relay
     hipStream_t stream = nullptr;
-    // the service's own descriptor / result buffers (pinned, coherent, mapped) and their device
-    // addresses: the same for every batch, so the parameter block rarely changes
-    vpcsum_desc_t* h_desc = nullptr;
-    uint32_t* h_out = nullptr;
-    uint8_t* h_status = nullptr;
-    vpcsum_desc_t* dh_desc = nullptr;
-    uint32_t* dh_out = nullptr;
-    uint8_t* dh_status = nullptr;
-    void* h_pre = nullptr;               // the aux buffer (kSvcAuxBytes): pre-images of a batch with F_PRE
+    // the service's own descriptor / result buffers (pinned, coherent, mapped): the same for every
+    // batch, so the parameter block rarely changes
+    vpcsum::Mapped<vpcsum_desc_t> h_desc;
+    vpcsum::Mapped<uint32_t> h_out;
+    vpcsum::Mapped<uint8_t> h_status;
+    vpcsum::Mapped<uint8_t> h_pre;       // the aux buffer (kSvcAuxBytes): pre-images of a batch with F_PRE
                                          // frames, or a parse batch's descriptors and tuples
-    void* dh_pre = nullptr;
     uint64_t par[3] = {0, 0, 0};         // arena, arena_len, arena_w last published
     bool par_valid = false;
     uint32_t posted = 0;                 // last batch published (seq)
     uint64_t idle_ticks = 0;             // 100 MHz ticks
     uint32_t grid = vpcsum::kServiceGrid;   // workgroups (VPCSUM_SVC_GRID: A/B tooling)
     uint32_t poll = 1;                      // relay poll mode: relaxed loads (VPCSUM_SVC_POLL: A/B tooling)
-    bool quiesce = false;                   // stop an idle grid before launched batches (VPCSUM_SVC_QUIESCE)
     bool on = false;
-    std::chrono::steady_clock::time_point last_post;   // the last batch posted (svc_quiesce)
     bool inline_desc = true;             // descriptors of <= kSvcInlineDesc frames ride in the command line
                                          // (VPCSUM_SVC_INLINE=0 turns it off: A/B tooling)
 #ifdef VPCSUM_SVC_STAMPS
@@ -338,8 +350,6 @@ int vpcsum_compute_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsu
     } VPC_CATCH("vpcsum_compute_async")
 }
 
-// NAT on device memory: the rewrite kernel, then (strict Java) the full recompute of the sums it
-// dirtied, written in place -- Java's getRawPacket(0) after the setters.
 }  // extern "C"
 
 // Two batches in flight on the device API (vpcsum.h vpcsum_pipe_*): launches alternate between two
@@ -430,6 +440,8 @@ int vpcsum_pipe_destroy(vpcsum_pipe_t* p) {
     } VPC_CATCH("vpcsum_pipe_destroy")
 }
 
+// NAT on device memory: the rewrite kernel, then (strict Java) the full recompute of the sums it
+// dirtied, written in place -- Java's getRawPacket(0) after the setters.
 static int nat_run(uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, const void* d_rw, int fmt,
                    uint32_t n, uint8_t* d_status, uint32_t nat_mode, hipStream_t s) {
     if (nat_mode & VPCSUM_NAT_STRICT_JAVA) {
@@ -656,16 +668,16 @@ static void slot_free(Slot& s) {
     if (s.d_desc) (void)hipFree(s.d_desc);
     if (s.d_out) (void)hipFree(s.d_out);
     if (s.d_status) (void)hipFree(s.d_status);
-    if (s.h_desc) (void)hipHostFree(s.h_desc);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_status) (void)hipHostFree(s.h_status);
+    s.h_desc.free();
+    s.h_out.free();
+    s.h_status.free();
     if (s.h_arena) (void)hipHostFree(s.h_arena);
-    if (s.h_foff) (void)hipHostFree(s.h_foff);
-    if (s.h_flen) (void)hipHostFree(s.h_flen);
-    if (s.h_rw) (void)hipHostFree(s.h_rw);
+    s.h_foff.free();
+    s.h_flen.free();
+    s.h_rw.free();
     if (s.d_rw) (void)hipFree(s.d_rw);
-    if (s.h_tu) (void)hipHostFree(s.h_tu);
-    if (s.h_hs) (void)hipHostFree(s.h_hs);
+    s.h_tu.free();
+    s.h_hs.free();
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = Slot();
@@ -675,17 +687,17 @@ static int slot_finish(vpcsum_ctx* c, Slot& s);
 
 static void svc_free(vpcsum_ctx* c) {
     Service& v = c->svc;
-    if (v.mb) __atomic_store_n(&v.mb->cmd, kSvcStop, __ATOMIC_RELEASE);
+    if (v.mb.p) __atomic_store_n(&v.mb.p->cmd, kSvcStop, __ATOMIC_RELEASE);
     if (v.stream) {
         (void)hipStreamSynchronize(v.stream);   // the grid sees kSvcStop within a poll interval
         (void)hipStreamDestroy(v.stream);
     }
     if (v.ctr) (void)hipFree(v.ctr);
-    if (v.mb) (void)hipHostFree(v.mb);
-    if (v.h_desc) (void)hipHostFree(v.h_desc);
-    if (v.h_out) (void)hipHostFree(v.h_out);
-    if (v.h_status) (void)hipHostFree(v.h_status);
-    if (v.h_pre) (void)hipHostFree(v.h_pre);
+    v.mb.free();
+    v.h_desc.free();
+    v.h_out.free();
+    v.h_status.free();
+    v.h_pre.free();
     c->svc = Service();
 }
 
@@ -699,40 +711,34 @@ int vpcsum_ctx_set_service(vpcsum_ctx_t* c, uint32_t idle_us) {
         svc_free(c);
         if (idle_us == 0) return 0;
         Service& v = c->svc;
-        const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
         hipError_t e = hipSuccess;
-        if ((e = hipHostMalloc((void**)&v.mb, sizeof(SvcMailbox), fl)) != hipSuccess ||
-            (e = hipHostGetDevicePointer((void**)&v.dmb, v.mb, 0)) != hipSuccess ||
-            (e = hipHostMalloc((void**)&v.h_desc, (size_t)c->max_pkts * sizeof(vpcsum_desc_t), fl)) != hipSuccess ||
-            (e = hipHostMalloc((void**)&v.h_out, (size_t)c->max_pkts * 4, fl)) != hipSuccess ||
-            (e = hipHostMalloc((void**)&v.h_status, (size_t)c->max_pkts, fl)) != hipSuccess ||
-            (e = hipHostMalloc((void**)&v.h_pre, kSvcAuxBytes, fl)) != hipSuccess ||
-            (e = hipHostGetDevicePointer((void**)&v.dh_pre, v.h_pre, 0)) != hipSuccess ||
-            (e = hipHostGetDevicePointer((void**)&v.dh_desc, v.h_desc, 0)) != hipSuccess ||
-            (e = hipHostGetDevicePointer((void**)&v.dh_out, v.h_out, 0)) != hipSuccess ||
-            (e = hipHostGetDevicePointer((void**)&v.dh_status, v.h_status, 0)) != hipSuccess ||
+        if ((e = v.mb.pin(sizeof(SvcMailbox))) != hipSuccess || (e = v.mb.map()) != hipSuccess ||
+            (e = v.h_desc.pin((size_t)c->max_pkts * sizeof(vpcsum_desc_t))) != hipSuccess ||
+            (e = v.h_out.pin((size_t)c->max_pkts * 4)) != hipSuccess ||
+            (e = v.h_status.pin((size_t)c->max_pkts)) != hipSuccess ||
+            (e = v.h_pre.pin(kSvcAuxBytes)) != hipSuccess ||
+            (e = v.h_pre.map()) != hipSuccess || (e = v.h_desc.map()) != hipSuccess ||
+            (e = v.h_out.map()) != hipSuccess || (e = v.h_status.map()) != hipSuccess ||
             (e = hipMalloc((void**)&v.ctr, 16)) != hipSuccess ||   // counter + command relay
             (e = hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking)) != hipSuccess) {
             svc_free(c);
             return hipfail(e, "vpcsum_ctx_set_service allocation");
         }
-        memset((void*)v.mb, 0, sizeof(SvcMailbox));
-        v.mb->desc = (uint64_t)(uintptr_t)v.dh_desc;
-        v.mb->out = (uint64_t)(uintptr_t)v.dh_out;
-        v.mb->status = (uint64_t)(uintptr_t)v.dh_status;
-        v.mb->pre = (uint64_t)(uintptr_t)v.dh_pre;
+        memset((void*)v.mb.p, 0, sizeof(SvcMailbox));
+        v.mb.p->desc = (uint64_t)(uintptr_t)v.h_desc.dev;
+        v.mb.p->out = (uint64_t)(uintptr_t)v.h_out.dev;
+        v.mb.p->status = (uint64_t)(uintptr_t)v.h_status.dev;
+        v.mb.p->pre = (uint64_t)(uintptr_t)v.h_pre.dev;
         v.idle_ticks = (uint64_t)idle_us * 100u;   // s_memrealtime runs at 100 MHz
         const char* gs = getenv("VPCSUM_SVC_GRID");   // A/B tooling: the grid's workgroups (1..256)
         if (gs && atoi(gs) >= 1 && atoi(gs) <= 256) v.grid = (uint32_t)atoi(gs);
         const char* pm = getenv("VPCSUM_SVC_POLL");   // 0: round 5's acquire loads
         if (pm) v.poll = (uint32_t)atoi(pm) & 7u;
-        const char* q = getenv("VPCSUM_SVC_QUIESCE");
-        v.quiesce = q && q[0] == '1';
         const char* inl = getenv("VPCSUM_SVC_INLINE");
         v.inline_desc = !(inl && inl[0] == '0');
         const char* clamp = getenv("VPCSUM_SVC_CLAMP");   // A/B tooling: 1 = clamped frame loads
         const char* reld = getenv("VPCSUM_SVC_RELEASE_DONE");   // A/B tooling: 1 = release on count / done
-        v.mb->opts = ((clamp && clamp[0] == '1') ? kSvcOptClampLoads : 0) | ((reld && reld[0] == '1') ? kSvcOptReleaseDone : 0);
+        v.mb.p->opts = ((clamp && clamp[0] == '1') ? kSvcOptClampLoads : 0) | ((reld && reld[0] == '1') ? kSvcOptReleaseDone : 0);
         v.on = true;
         return 0;
     } VPC_CATCH("vpcsum_ctx_set_service")
@@ -763,17 +769,15 @@ int vpcsum_ctx_create(int device, uint64_t max_arena_bytes, uint32_t max_pkts, v
                 (e = hipMalloc((void**)&s.d_desc, (size_t)max_pkts * sizeof(vpcsum_desc_t))) != hipSuccess ||
                 (e = hipMalloc((void**)&s.d_out, (size_t)max_pkts * 4)) != hipSuccess ||
                 (e = hipMalloc((void**)&s.d_status, (size_t)max_pkts)) != hipSuccess ||
-                (e = hipHostMalloc((void**)&s.h_desc, (size_t)max_pkts * sizeof(vpcsum_desc_t), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-                (e = hipHostMalloc((void**)&s.h_out, (size_t)max_pkts * 4, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-                (e = hipHostMalloc((void**)&s.h_status, (size_t)max_pkts, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-                (e = hipHostGetDevicePointer((void**)&s.dh_desc, s.h_desc, 0)) != hipSuccess ||
-                (e = hipHostGetDevicePointer((void**)&s.dh_out, s.h_out, 0)) != hipSuccess ||
-                (e = hipHostGetDevicePointer((void**)&s.dh_status, s.h_status, 0)) != hipSuccess ||
+                (e = s.h_desc.pin((size_t)max_pkts * sizeof(vpcsum_desc_t))) != hipSuccess ||
+                (e = s.h_out.pin((size_t)max_pkts * 4)) != hipSuccess ||
+                (e = s.h_status.pin((size_t)max_pkts)) != hipSuccess ||
+                (e = s.h_desc.map()) != hipSuccess || (e = s.h_out.map()) != hipSuccess ||
+                (e = s.h_status.map()) != hipSuccess ||
                 (e = hipHostMalloc((void**)&s.h_arena, max_arena_bytes + 64, 0)) != hipSuccess ||
-                (e = hipHostMalloc((void**)&s.h_foff, (size_t)max_pkts * 8, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-                (e = hipHostMalloc((void**)&s.h_flen, (size_t)max_pkts * 4, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-                (e = hipHostGetDevicePointer((void**)&s.dh_foff, s.h_foff, 0)) != hipSuccess ||
-                (e = hipHostGetDevicePointer((void**)&s.dh_flen, s.h_flen, 0)) != hipSuccess ||
+                (e = s.h_foff.pin((size_t)max_pkts * 8)) != hipSuccess ||
+                (e = s.h_flen.pin((size_t)max_pkts * 4)) != hipSuccess ||
+                (e = s.h_foff.map()) != hipSuccess || (e = s.h_flen.map()) != hipSuccess ||
                 (e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess ||
                 (e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) {
                 for (auto& t : c->slots) slot_free(t);
@@ -841,7 +845,7 @@ int vpcsum_ctx_register_arena(vpcsum_ctx_t* c, void* h_arena, uint64_t len) {
 // Caller holds c->mu on c's device.
 static int ctx_quiesce_zero_copy(vpcsum_ctx* c) {
     for (auto& s : c->slots)
-        if (s.busy && s.zero_copy && slot_finish(c, s) != 0) return -1;
+        if (s.busy && s.batch.zero_copy && slot_finish(c, s) != 0) return -1;
     c->svc.par_valid = false;
     return 0;
 }
@@ -878,14 +882,14 @@ static uint8_t* mapped_dev(vpcsum_ctx* c, const uint8_t* p, uint64_t len) {
 // version trusted hipPointerGetAttributes here; DESIGN_HISTORY.md "Round 6: the intermittent fault").
 static bool is_registered(vpcsum_ctx* c, const uint8_t* p, uint64_t len) { return mapped_dev(c, p, len) != nullptr; }
 
-static uint32_t svc_done(const Service& v) { return __atomic_load_n(&v.mb->done, __ATOMIC_ACQUIRE); }
+static uint32_t svc_done(const Service& v) { return __atomic_load_n(&v.mb.p->done, __ATOMIC_ACQUIRE); }
 
 // (Re)start the service grid: it treats batches after `seen` as new.  Only called while no grid
 // of this context runs (stream idle), so the finished-wave counter can be cleared first.
 static int svc_launch(vpcsum_ctx* c, uint32_t seen) {
     Service& v = c->svc;
     VPC_CHECK(hipMemsetAsync(v.ctr, 0, 16, v.stream), "service counter / relay reset");
-    VPC_CHECK(launch_service(v.dmb, v.ctr, seen, v.idle_ticks, v.stream, v.grid, v.poll), "service launch");
+    VPC_CHECK(launch_service(v.mb.dev, v.ctr, seen, v.idle_ticks, v.stream, v.grid, v.poll), "service launch");
     ++c->svc_launches;
     return 0;
 }
@@ -927,7 +931,7 @@ static int svc_wait(vpcsum_ctx* c, uint32_t seq) {
     {
         static bool reg = false;
         if (!reg) { reg = true; atexit(stamps_print); }
-        const uint64_t* s = (const uint64_t*)v.mb->stamp;
+        const uint64_t* s = (const uint64_t*)v.mb.p->stamp;
         const uint64_t s0 = s[0];
         const uint32_t n = v.t_n;
         g_stamp_d[0][n].push_back((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -940,147 +944,140 @@ static int svc_wait(vpcsum_ctx* c, uint32_t seq) {
     return 0;
 }
 
+// Complete the slot's batch: wait for it, hand its results to the caller's buffers, and forget it.
 static int slot_finish(vpcsum_ctx* c, Slot& s) {
     if (!s.busy) return 0;
-    if (s.svc_seq) {
-        if (svc_wait(c, s.svc_seq) != 0) return -1;
+    const Batch& b = s.batch;
+    const bool svc = b.svc_seq != 0;   // the results are in the service's buffers
+    if (svc) {
+        if (svc_wait(c, b.svc_seq) != 0) return -1;
     } else {
         VPC_CHECK(hipEventSynchronize(s.done), "hipEventSynchronize");
     }
-    if (s.kind == 1) {
-        // NAT: a staged batch's rewritten headers (L3 header through the L4 checksum field)
-        // go back into the caller's frames; zero-copy batches rewrote them in place
-        if (!s.zero_copy && s.user_arena) {
-            for (uint32_t i = 0; i < s.n; ++i) {
-                if (s.h_status[i] & VPCSUM_S_BAD_DESC) continue;
-                const vpcsum_desc_t& d = s.user_desc[i];
-                const int fld = d.l4_proto == 6 ? 16 : d.l4_proto == 17 ? 6 : (d.l4_proto == 1 || d.l4_proto == 58) ? 2 : -1;
-                uint32_t end = d.l3_ver == 4 ? 20 : 40;
-                if (fld >= 0 && d.l3_len >= d.l4_off + fld + 2) end = std::max<uint32_t>(end, d.l4_off + fld + 2u);
-                end = std::min<uint32_t>(end, d.l3_len);
-                memcpy(s.user_arena + d.l3_off, s.h_arena + s.h_desc[i].l3_off, end);
+    const uint32_t* res_out = svc ? c->svc.h_out.p : s.h_out.p;
+    const uint8_t* res_status = svc ? c->svc.h_status.p : s.h_status.p;
+    const uint8_t* aux = c->svc.h_pre.p;
+    if (b.user_status) memcpy(b.user_status, res_status, b.n);
+    switch (b.kind) {
+    case BatchKind::Nat:
+        // a staged batch's rewritten headers (L3 header through the L4 checksum field) go back
+        // into the caller's frames; zero-copy batches rewrote them in place
+        if (!b.zero_copy && b.user_arena) {
+            for (uint32_t i = 0; i < b.n; ++i) {
+                if (res_status[i] & VPCSUM_S_BAD_DESC) continue;
+                const vpcsum_desc_t& d = b.user_desc[i];
+                memcpy(b.user_arena + d.l3_off, s.h_arena + s.h_desc.p[i].l3_off, nat_header_end(d));
             }
         }
-        if (s.user_status) memcpy(s.user_status, s.h_status, s.n);
-        s.busy = false;
-        return 0;
-    }
-    if (s.kind == 2) {   // parse: descriptors, status and tuples were written to the pinned staging
-        const bool svc = s.svc_seq != 0;   // or, through the service grid, to its aux buffer
-        const uint8_t* aux = (const uint8_t*)c->svc.h_pre;
-        if (s.user_desc_out)
-            memcpy(s.user_desc_out, svc ? aux : (const uint8_t*)s.h_desc, (size_t)s.n * sizeof(vpcsum_desc_t));
-        if (s.user_status) memcpy(s.user_status, svc ? c->svc.h_status : s.h_status, s.n);
-        if (s.user_tuples)
-            memcpy(s.user_tuples, svc ? aux + (size_t)kSvcBatchMax * sizeof(vpcsum_desc_t) : (const uint8_t*)s.h_tu,
-                   (size_t)s.n * sizeof(vpcsum_tuple_t));
-        s.busy = false;
-        s.svc_seq = 0;
-        return 0;
-    }
-    const uint32_t* res_out = s.svc_seq ? c->svc.h_out : s.h_out;
-    const uint8_t* res_status = s.svc_seq ? c->svc.h_status : s.h_status;
-    if (s.user_out) memcpy(s.user_out, res_out, (size_t)s.n * 4);
-    if (s.user_status) memcpy(s.user_status, res_status, s.n);
-    if (s.user_hsum)   // a verify batch's header sums: the service's aux buffer, or the slot's staging
-        memcpy(s.user_hsum, s.svc_seq ? (const void*)c->svc.h_pre : (const void*)s.h_hs, (size_t)s.n * sizeof(vpcsum_hsum_t));
-    s.user_hsum = nullptr;
-    if ((s.mode & VPCSUM_MODE_WRITE) && s.user_arena && !s.zero_copy) {
-        // place the GPU results into the caller's frames (big endian, as ByteArray.int16)
-        for (uint32_t i = 0; i < s.n; ++i) {
-            const vpcsum_desc_t& d = s.user_desc[i];
-            if (res_status[i] & VPCSUM_S_BAD_DESC) continue;
-            uint8_t* l3 = s.user_arena + d.l3_off;
-            const uint32_t w = res_out[i];
-            if (d.flags & VPCSUM_F_IP) { l3[10] = (uint8_t)(w >> 8); l3[11] = (uint8_t)w; }
-            if (d.flags & (VPCSUM_F_L4 | VPCSUM_F_L4P)) {
-                const int fld = d.l4_proto == 6 ? 16 : d.l4_proto == 17 ? 6 : 2;
-                l3[d.l4_off + fld] = (uint8_t)(w >> 24);
-                l3[d.l4_off + fld + 1] = (uint8_t)(w >> 16);
+        break;
+    case BatchKind::Parse:   // descriptors and tuples: the pinned staging, or the service's aux buffer
+        if (b.user_desc_out)
+            memcpy(b.user_desc_out, svc ? aux : (const uint8_t*)s.h_desc.p, (size_t)b.n * sizeof(vpcsum_desc_t));
+        if (b.user_tuples)
+            memcpy(b.user_tuples, svc ? aux + (size_t)kSvcBatchMax * sizeof(vpcsum_desc_t) : (const uint8_t*)s.h_tu.p,
+                   (size_t)b.n * sizeof(vpcsum_tuple_t));
+        break;
+    case BatchKind::Csum:
+        if (b.user_out) memcpy(b.user_out, res_out, (size_t)b.n * 4);
+        if (b.user_hsum)   // a verify batch's header sums: the service's aux buffer, or the slot's staging
+            memcpy(b.user_hsum, svc ? (const void*)aux : (const void*)s.h_hs.p, (size_t)b.n * sizeof(vpcsum_hsum_t));
+        if ((b.mode & VPCSUM_MODE_WRITE) && b.user_arena && !b.zero_copy) {
+            // place the GPU results into the caller's frames (big endian, as ByteArray.int16)
+            for (uint32_t i = 0; i < b.n; ++i) {
+                const vpcsum_desc_t& d = b.user_desc[i];
+                if (res_status[i] & VPCSUM_S_BAD_DESC) continue;
+                uint8_t* l3 = b.user_arena + d.l3_off;
+                const uint32_t w = res_out[i];
+                if (d.flags & VPCSUM_F_IP) { l3[10] = (uint8_t)(w >> 8); l3[11] = (uint8_t)w; }
+                if (d.flags & (VPCSUM_F_L4 | VPCSUM_F_L4P)) {
+                    const int fld = l4_field_host(d.l4_proto);
+                    if (fld < 0) continue;   // no L4 sum: the kernel refused the descriptor (BAD above)
+                    l3[d.l4_off + fld] = (uint8_t)(w >> 24);
+                    l3[d.l4_off + fld + 1] = (uint8_t)(w >> 16);
+                }
             }
         }
+        break;
     }
+    s.batch = Batch();
     s.busy = false;
-    s.svc_seq = 0;
+    return 0;
+}
+
+// The next ticket and its slot, whatever batch the slot still holds finished first.  nullptr: that
+// batch failed (the message is set).
+static Slot* slot_acquire(vpcsum_ctx* c, uint64_t* t) {
+    *t = c->next_ticket++;
+    Slot& s = c->slots[*t & 1];
+    if (s.busy && slot_finish(c, s) != 0) return nullptr;
+    return &s;
+}
+
+// Slot s now owns batch b, every field of it (what b does not name is reset, so nothing of the
+// slot's previous batch survives).  A launched batch -- one not handed to the service -- is
+// complete when `done`, recorded here behind its last launch or copy, has passed.
+static int slot_commit(Slot& s, const Batch& b, uint64_t* ticket) {
+    if (!b.svc_seq) VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
+    s.batch = b;
+    s.busy = true;
+    *ticket = b.ticket;
     return 0;
 }
 
 // The slot's per-packet entry staging (NAT rewrites, pre-images: at most 48 B each), pinned and
 // mapped plus a device copy, allocated with the context's first batch that carries entries.
 static int slot_rw_alloc(vpcsum_ctx* c, Slot& s, const char* what) {
-    if (s.h_rw) return 0;
-    hipError_t e = hipSuccess;
+    if (s.h_rw.p) return 0;
     const size_t bytes = (size_t)c->max_pkts * sizeof(vpcsum_nat_t);
-    if ((e = hipHostMalloc((void**)&s.h_rw, bytes, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&s.dh_rw, s.h_rw, 0)) != hipSuccess ||
-        (e = hipMalloc((void**)&s.d_rw, bytes)) != hipSuccess) {
-        if (s.h_rw) (void)hipHostFree(s.h_rw);
-        if (s.d_rw) (void)hipFree(s.d_rw);
-        s.h_rw = s.dh_rw = s.d_rw = nullptr;
-        return hipfail(e, what);
+    hipError_t e = s.h_rw.alloc(bytes);
+    if (e == hipSuccess && (e = hipMalloc((void**)&s.d_rw, bytes)) != hipSuccess) {
+        s.h_rw.free();
+        s.d_rw = nullptr;
     }
-    return 0;
+    return e == hipSuccess ? 0 : hipfail(e, what);
 }
 
-static int l4_field_host(int proto) { return proto == 6 ? 16 : proto == 17 ? 6 : (proto == 1 || proto == 58) ? 2 : -1; }
+// Zero-copy batches of up to kZeroCopyWaveTeams packets run one wave per packet (variant 12, 64
+// lanes x 4 predicated loads): the batch is a few PCIe round trips deep instead of K2's per-unit
+// iterations, and no chunk is read twice over PCIe.
+static int zero_copy_variant(uint32_t n) { return n <= kZeroCopyWaveTeams ? 12 : 0; }
 
 // The service runs one batch at a time: the previous one done, its results handed over, before its
-// buffers are refilled.
+// buffers are refilled.  (An idle grid stays resident beside launched batches: the stop round 5 had
+// here is gone, DESIGN_HISTORY.md "Round 5: experiments" and "The context batch path in one piece".)
 static int svc_drain(vpcsum_ctx* c) {
     for (auto& o : c->slots)
-        if (o.busy && o.svc_seq && slot_finish(c, o) != 0) return -1;
-    return 0;
-}
-
-// Before a launched zero-copy batch (more than kSvcBatchMax frames, or a form the grid does not
-// take), round 5 stopped a resident grid that had had no batch for kSvcKeep: with an idle grid
-// resident, launched batches ran 6-50% slower.  The cause (round 6, tools/svc_interference.cpp,
-// profiles/r06e_svc_interference.json, r06f_svc_poll.json) was the grid's relay pollers: 31
-// workgroups re-reading the relay word with an agent-scope ACQUIRE load, each one a cache
-// invalidate, while a sleeping grid of the same shape cost nothing.  With relaxed relay loads (the
-// acquire fence after the poll orders the batch, kernels.hip k_csum_service) a resident grid costs
-// the launched batches nothing measurable, so it stays: the stop is now opt-in
-// (VPCSUM_SVC_QUIESCE=1, the A/B of round 5's policy) and a small flush after a large one no
-// longer pays a grid launch.
-constexpr auto kSvcKeep = std::chrono::microseconds(1000);
-static int svc_quiesce(vpcsum_ctx* c) {
-    Service& v = c->svc;
-    if (!v.quiesce || !v.on || hipStreamQuery(v.stream) == hipSuccess) return 0;   // off, or no grid resident
-    if (std::chrono::steady_clock::now() - v.last_post < kSvcKeep) return 0;
-    if (svc_drain(c) != 0) return -1;
-    __atomic_store_n(&v.mb->cmd, kSvcStop | v.posted, __ATOMIC_RELEASE);
-    VPC_CHECK(hipStreamSynchronize(v.stream), "service stop");
+        if (o.busy && o.batch.svc_seq && slot_finish(c, o) != 0) return -1;
     return 0;
 }
 
 // Hand a zero-copy batch to the low-latency service (c->svc.on, n <= kSvcBatchMax): one batch at
 // a time; descriptors (and pre-images) into the service's buffers, the parameter block if it
 // changed, then the command word.  `base` is the device address of h_arena[0].  Caller holds c->mu
-// on c's device; slot s (ticket t) is free.
-// frames: h_desc is the service's own buffer, filled with SvcFrameRec records (raw frames); parse:
-// the frames are parsed only (vpcsum_ctx_parse_frames).
-static int svc_post(vpcsum_ctx* c, Slot& s, uint64_t t, uint8_t* h_arena, uint64_t arena_len, uint8_t* base,
-                    const vpcsum_desc_t* h_desc, uint32_t n, uint32_t* h_out, uint8_t* h_status, uint32_t mode,
-                    const void* h_pre, uint32_t pre_fmt, uint64_t* ticket, bool frames = false, bool parse = false,
-                    bool hsum = false) {
+// on c's device; slot s is free and takes batch b (its n and mode are the batch's).
+// form: kSvcFrames -- h_desc is the service's own buffer, filled with SvcFrameRec records (raw
+// frames) -- with kSvcParse (parsed only, vpcsum_ctx_parse_frames) or kSvcHsum.
+static int svc_post(vpcsum_ctx* c, Slot& s, Batch b, const uint8_t* h_arena, uint64_t arena_len, uint8_t* base,
+                    const vpcsum_desc_t* h_desc, const void* h_pre, uint32_t pre_fmt, uint64_t form, uint64_t* ticket) {
     Service& v = c->svc;
-    SvcMailbox* mb = v.mb;
-    if (!frames) memcpy(v.h_desc, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-    uint64_t cmd = (frames ? kSvcFrames : 0) | (parse ? kSvcParse : 0) | (hsum ? kSvcHsum : 0);
+    SvcMailbox* mb = v.mb.p;
+    const uint32_t n = b.n, mode = b.mode;
+    if (!(form & kSvcFrames)) memcpy(v.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+    uint64_t cmd = form;
     if (h_pre) {
         // the pre-images, each F_PRE frame's stored L4 sum copied into its entry's spare bytes
         // (vpcsum_pre4_t rsv[1..2], vpcsum_pre_t rsv[0..1]): the kernel takes the sum from there,
         // so a batch re-run by a fresh grid (svc_wait) computes from the same input
         const size_t esz = pre_fmt == VPCSUM_PRE_FMT_PRE ? sizeof(vpcsum_pre_t) : sizeof(vpcsum_pre4_t);
         const size_t at = pre_fmt == VPCSUM_PRE_FMT_PRE ? offsetof(vpcsum_pre_t, rsv) : offsetof(vpcsum_pre4_t, rsv) + 1;
-        memcpy(v.h_pre, h_pre, (size_t)n * esz);
+        memcpy(v.h_pre.p, h_pre, (size_t)n * esz);
         for (uint32_t i = 0; i < n; ++i) {
             const vpcsum_desc_t& d = h_desc[i];
             const int fld = l4_field_host(d.l4_proto);
-            if (!(d.flags & VPCSUM_F_PRE) || fld < 0 || d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off ||
+            if (!(d.flags & VPCSUM_F_PRE) || fld < 0 || !desc_in_arena(d, arena_len) ||
                 (uint32_t)d.l4_off + fld + 2u > d.l3_len)
                 continue;   // no L4 sum to update, or refused by the kernel
-            memcpy((uint8_t*)v.h_pre + (size_t)i * esz + at, h_arena + d.l3_off + d.l4_off + fld, 2);
+            memcpy((uint8_t*)v.h_pre.p + (size_t)i * esz + at, h_arena + d.l3_off + d.l4_off + fld, 2);
         }
         cmd |= kSvcPre | (pre_fmt == VPCSUM_PRE_FMT_PRE ? kSvcPreFmt : 0);
     }
@@ -1116,35 +1113,23 @@ static int svc_post(vpcsum_ctx* c, Slot& s, uint64_t t, uint8_t* h_arena, uint64
 #endif
     __atomic_store_n(&mb->cmd, cmd, __ATOMIC_RELEASE);
     v.posted = seq;
-    v.last_post = std::chrono::steady_clock::now();
     ++c->svc_batches;
     if (hipStreamQuery(v.stream) == hipSuccess && svc_launch(c, seq - 1) != 0) return -1;
-    s.zero_copy = true;
-    s.svc_seq = seq;
-    s.kind = 0;
-    s.busy = true;
-    s.ticket = t;
-    s.n = n;
-    s.mode = mode;
-    s.user_arena = h_arena;
-    s.user_desc = h_desc;
-    s.user_out = h_out;
-    s.user_status = h_status;
-    *ticket = t;
-    return 0;
+    b.zero_copy = true;
+    b.svc_seq = seq;
+    return slot_commit(s, b, ticket);
 }
 
 // A small batch of raw frames (egress, RX verify or RX parse) to the service grid: one SvcFrameRec
 // per frame in the service's descriptor buffer -- offset, length, and the frame's own flags
 // (h_flags) or `flags` for all -- then svc_post.  The results stay in the service's buffers until
 // slot_finish hands them over; the frames themselves are written in place through the mapping.
-static int svc_post_frames(vpcsum_ctx* c, Slot& s, uint64_t t, const uint8_t* h_arena, uint64_t arena_len, uint8_t* base,
+static int svc_post_frames(vpcsum_ctx* c, Slot& s, const Batch& b, uint64_t arena_len, uint8_t* base,
                            const uint64_t* h_off, const uint32_t* h_len, const uint8_t* h_flags, uint8_t flags,
-                           uint32_t n, uint32_t* h_out, uint8_t* h_status, uint32_t mode, bool parse, uint64_t* ticket,
-                           bool hsum = false) {
+                           uint64_t form, uint64_t* ticket) {
     if (svc_drain(c) != 0) return -1;
-    SvcFrameRec* r = reinterpret_cast<SvcFrameRec*>(c->svc.h_desc);
-    for (uint32_t i = 0; i < n; ++i) {
+    SvcFrameRec* r = reinterpret_cast<SvcFrameRec*>(c->svc.h_desc.p);
+    for (uint32_t i = 0; i < b.n; ++i) {
         SvcFrameRec x;
         memset(&x, 0, sizeof(x));
         x.off = h_off[i];
@@ -1152,12 +1137,7 @@ static int svc_post_frames(vpcsum_ctx* c, Slot& s, uint64_t t, const uint8_t* h_
         x.flags = h_flags ? h_flags[i] : flags;
         memcpy(&r[i], &x, sizeof(x));
     }
-    if (svc_post(c, s, t, const_cast<uint8_t*>(h_arena), arena_len, base, c->svc.h_desc, n, h_out, h_status, mode, nullptr,
-                 0, ticket, true, parse, hsum) != 0)
-        return -1;
-    s.user_arena = nullptr;
-    s.user_desc = nullptr;
-    return 0;
+    return svc_post(c, s, b, nullptr, arena_len, base, c->svc.h_desc.p, nullptr, 0, kSvcFrames | form, ticket);
 }
 
 int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc, uint32_t n,
@@ -1169,24 +1149,19 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
         if (mode & ~(VPCSUM_MODE_VERIFY | VPCSUM_MODE_WRITE)) return fail("vpcsum_ctx_submit: bad mode 0x%x", mode);
         std::lock_guard<std::mutex> lk(c->mu);
         VPC_ON_DEVICE(c->device);
-        const uint64_t t = c->next_ticket++;
-        Slot& s = c->slots[t & 1];
-        if (s.busy && slot_finish(c, s) != 0) return -1;
+        Batch b;
+        Slot* slot = slot_acquire(c, &b.ticket);
+        if (!slot) return -1;
+        Slot& s = *slot;
+        b.n = n;
+        b.mode = mode;
+        b.user_arena = h_arena;
+        b.user_desc = h_desc;
+        b.user_out = h_out;
+        b.user_status = h_status;
 
-        // byte span the descriptors touch (16-B aligned so device alignment == host alignment)
-        uint64_t lo = UINT64_MAX, hi = 0, used = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            const vpcsum_desc_t& d = h_desc[i];
-            if (d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off) continue;   // kernel flags it BAD
-            lo = std::min(lo, d.l3_off);
-            hi = std::max(hi, d.l3_off + d.l3_len);
-            used += d.l3_len + 16;
-        }
-        if (lo == UINT64_MAX) { lo = 0; hi = 0; }
-        lo &= ~(uint64_t)15;
-        const uint64_t span = hi - lo;
-        s.zero_copy = false;
-
+        const BatchSpan sp = batch_span(h_desc, n, arena_len);
+        const uint64_t lo = sp.lo, span = sp.hi - sp.lo;
         uint8_t* dev_arena = span ? mapped_dev(c, h_arena + lo, span) : nullptr;
         if (dev_arena) {
             // Zero-copy: the frames live in a page-locked, mapped arena (an AF_XDP umem).  The
@@ -1196,49 +1171,34 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
             uint8_t* base = dev_arena - lo;   // device address of h_arena[0]
             if (c->svc.on && n <= kSvcBatchMax) {
                 if (svc_drain(c) != 0) return -1;
-                return svc_post(c, s, t, h_arena, arena_len, base, h_desc, n, h_out, h_status, mode, nullptr, 0, ticket);
+                return svc_post(c, s, b, h_arena, arena_len, base, h_desc, nullptr, 0, 0, ticket);
             }
-            if (svc_quiesce(c) != 0) return -1;
-            memcpy(s.h_desc, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-            // up to kZeroCopyWaveTeams packets: one wave per packet (variant 12, 64 lanes x 4
-            // predicated loads), so the batch is a few PCIe round trips deep instead of K2's per-unit
-            // iterations, and no chunk is read twice over PCIe
-            const int variant = n <= kZeroCopyWaveTeams ? 12 : 0;
+            memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
             // no out words asked for (an ingress verify: the status bytes are the result): none written
-            VPC_CHECK(launch_csum(base, arena_len, s.dh_desc, n, h_out ? s.dh_out : nullptr, s.dh_status, nullptr,
-                                  mode & VPCSUM_MODE_VERIFY, (mode & VPCSUM_MODE_WRITE) ? base : nullptr, variant, 0,
-                                  s.stream),
+            VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
+                                  mode & VPCSUM_MODE_VERIFY, (mode & VPCSUM_MODE_WRITE) ? base : nullptr,
+                                  zero_copy_variant(n), 0, s.stream),
                       "checksum launch (zero-copy)");
-            s.zero_copy = true;
+            b.zero_copy = true;
         } else {
-            const bool gather = span > 2 * used + (64u << 10);
+            const bool gather = span > 2 * sp.used + (64u << 10);
             uint64_t dev_len = span;
             if (gather) {
                 // sparse batch in a large pageable arena: gather the touched 16-B blocks only
-                uint64_t pos = 0;
-                for (uint32_t i = 0; i < n; ++i) {
-                    const vpcsum_desc_t& d = h_desc[i];
-                    s.h_desc[i] = d;
-                    if (d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off) { s.h_desc[i].l3_off = UINT64_MAX; continue; }
-                    const uint64_t a0 = d.l3_off & ~(uint64_t)15;
-                    const uint64_t a1 = std::min<uint64_t>((d.l3_off + d.l3_len + 15) & ~(uint64_t)15, arena_len);
-                    if (pos + (a1 - a0) > c->max_arena) return fail("vpcsum_ctx_submit: gathered batch exceeds capacity");
-                    memcpy(s.h_arena + pos, h_arena + a0, a1 - a0);
-                    s.h_desc[i].l3_off = pos + (d.l3_off - a0);
-                    pos += (a1 - a0 + 15) & ~(uint64_t)15;
-                }
-                dev_len = pos;
+                const int64_t staged = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena, c->max_arena);
+                if (staged < 0) return fail("vpcsum_ctx_submit: gathered batch exceeds capacity");
+                dev_len = (uint64_t)staged;
             } else {
                 if (span > c->max_arena) return fail("vpcsum_ctx_submit: batch spans %llu bytes > capacity %llu",
                                                      (unsigned long long)span, (unsigned long long)c->max_arena);
                 // descriptors rebased to the device copy of [lo, hi)
                 for (uint32_t i = 0; i < n; ++i) {
-                    s.h_desc[i] = h_desc[i];
-                    if (h_desc[i].l3_off >= lo) s.h_desc[i].l3_off = h_desc[i].l3_off - lo;
-                    else s.h_desc[i].l3_off = UINT64_MAX;   // out of span -> BAD in the kernel
+                    s.h_desc.p[i] = h_desc[i];
+                    if (h_desc[i].l3_off >= lo) s.h_desc.p[i].l3_off = h_desc[i].l3_off - lo;
+                    else s.h_desc.p[i].l3_off = UINT64_MAX;   // out of span -> BAD in the kernel
                 }
             }
-            VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
+            VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
                       "H2D descriptors");
             if (dev_len) {
                 const uint8_t* src = gather ? s.h_arena : h_arena + lo;
@@ -1254,21 +1214,10 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
                                   mode & VPCSUM_MODE_VERIFY, nullptr, 0, 0, s.stream),
                       "checksum launch");
             if (want_out)
-                VPC_CHECK(hipMemcpyAsync(s.h_out, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
-            VPC_CHECK(hipMemcpyAsync(s.h_status, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
+                VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
+            VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
         }
-        VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
-        s.kind = 0;
-        s.busy = true;
-        s.ticket = t;
-        s.n = n;
-        s.mode = mode;
-        s.user_arena = h_arena;
-        s.user_desc = h_desc;
-        s.user_out = h_out;
-        s.user_status = h_status;
-        *ticket = t;
-        return 0;
+        return slot_commit(s, b, ticket);
     } VPC_CATCH("vpcsum_ctx_submit")
 }
 
@@ -1289,88 +1238,63 @@ int vpcsum_ctx_submit_pre(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
         const bool full = npre < n;   // descriptors the checksum kernel sums in full
         std::lock_guard<std::mutex> lk(c->mu);
         VPC_ON_DEVICE(c->device);
-        const uint64_t t = c->next_ticket++;
-        Slot& s = c->slots[t & 1];
-        if (s.busy && slot_finish(c, s) != 0) return -1;
-        uint64_t lo = UINT64_MAX, hi = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            const vpcsum_desc_t& d = h_desc[i];
-            if (d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off) continue;   // the kernels flag it BAD
-            lo = std::min(lo, d.l3_off);
-            hi = std::max(hi, d.l3_off + d.l3_len);
-        }
-        if (lo == UINT64_MAX) { lo = 0; hi = 0; }
-        lo &= ~(uint64_t)15;
-        uint8_t* dev_arena = hi > lo ? mapped_dev(c, h_arena + lo, hi - lo) : nullptr;
+        Batch b;
+        Slot* slot = slot_acquire(c, &b.ticket);
+        if (!slot) return -1;
+        Slot& s = *slot;
+        b.n = n;
+        b.mode = mode;
+        b.user_arena = h_arena;
+        b.user_desc = h_desc;
+        b.user_out = h_out;
+        b.user_status = h_status;
+        const BatchSpan sp = batch_span(h_desc, n, arena_len);
+        uint8_t* dev_arena = sp.hi > sp.lo ? mapped_dev(c, h_arena + sp.lo, sp.hi - sp.lo) : nullptr;
+        uint8_t* base = dev_arena ? dev_arena - sp.lo : nullptr;   // device address of h_arena[0]
         const uint32_t wr = mode & VPCSUM_MODE_WRITE;
         // a small flush from the registered umem: the service grid, F_PRE frames and the others in
         // one batch (kernels.hip svc_pre_packet)
         if (dev_arena && c->svc.on && n <= kSvcBatchMax) {
             if (svc_drain(c) != 0) return -1;
-            return svc_post(c, s, t, h_arena, arena_len, dev_arena - lo, h_desc, n, h_out, h_status, mode, h_pre, pre_fmt,
-                            ticket);
+            return svc_post(c, s, b, h_arena, arena_len, base, h_desc, h_pre, pre_fmt, 0, ticket);
         }
         if (slot_rw_alloc(c, s, "vpcsum_ctx_submit_pre allocation") != 0) return -1;
-        memcpy(s.h_rw, h_pre, (size_t)n * esz);
+        memcpy(s.h_rw.p, h_pre, (size_t)n * esz);
         if (dev_arena) {
             // registered arena (umem): in place; an F_PRE packet's header is all that crosses PCIe
-            if (svc_quiesce(c) != 0) return -1;
-            uint8_t* base = dev_arena - lo;
-            memcpy(s.h_desc, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+            memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
             if (full)
-                VPC_CHECK(launch_csum(base, arena_len, s.dh_desc, n, s.dh_out, s.dh_status, nullptr, VPCSUM_MODE_COMPUTE,
-                                      wr ? base : nullptr, n <= kZeroCopyWaveTeams ? 12 : 0, 0, s.stream),
+                VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, s.h_out.dev, s.h_status.dev, nullptr, VPCSUM_MODE_COMPUTE,
+                                      wr ? base : nullptr, zero_copy_variant(n), 0, s.stream),
                           "checksum launch (zero-copy)");
-            VPC_CHECK(launch_pre(base, arena_len, s.dh_desc, s.dh_rw, (int)pre_fmt, n, s.dh_out, s.dh_status, wr, s.stream),
+            VPC_CHECK(launch_pre(base, arena_len, s.h_desc.dev, s.h_rw.dev, (int)pre_fmt, n, s.h_out.dev, s.h_status.dev, wr, s.stream),
                       "pre-image launch (zero-copy)");
-            s.zero_copy = true;
+            b.zero_copy = true;
         } else {
             // staged: each packet's 16-B blocks gathered into the pinned staging -- of an F_PRE
-            // packet only its header through the L4 checksum field (its descriptor's l3_len cut to
-            // that: the kernel reads no further), unless it is UDP with a stored 0, which is summed
-            // in full
-            uint64_t pos = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                const vpcsum_desc_t& d = h_desc[i];
-                s.h_desc[i] = d;
-                if (d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off) { s.h_desc[i].l3_off = UINT64_MAX; continue; }
-                uint32_t take = d.l3_len;
-                const int fld = l4_field_host(d.l4_proto);
-                if ((d.flags & VPCSUM_F_PRE) && fld >= 0 && (uint32_t)d.l4_off + fld + 2u <= d.l3_len) {
-                    const uint8_t* f = h_arena + d.l3_off + d.l4_off + fld;
-                    if (!(d.l4_proto == 17 && f[0] == 0 && f[1] == 0)) {
-                        // through the checksum field, or through the L4 header a header-sum entry covers
-                        const uint8_t* e = (const uint8_t*)h_pre + (size_t)i * esz;
-                        const uint8_t emask = e[pre_fmt == VPCSUM_PRE_FMT_PRE ? offsetof(vpcsum_pre_t, mask)
-                                                                               : offsetof(vpcsum_pre4_t, mask)];
-                        const uint32_t hl = (emask & VPCSUM_PRE_HSUM) ? e[offsetof(vpcsum_hsum_t, hlen)] : 0u;
-                        take = std::max<uint32_t>(d.l3_ver == 4 ? 20u : 40u,
-                                                  (uint32_t)d.l4_off + std::max<uint32_t>(fld + 2u, hl));
-                        take = std::min<uint32_t>(take, d.l3_len);
-                        s.h_desc[i].l3_len = (uint16_t)take;
-                        if (emask & VPCSUM_PRE_HSUM) {
-                            // the kernel checks the record's segment length against the descriptor's,
-                            // which is cut here: check it against the real one on the host, and hand the
-                            // kernel the cut length (or, on a mismatch, a record it refuses)
-                            vpcsum_hsum_t hs;
-                            uint8_t* se = (uint8_t*)s.h_rw + (size_t)i * esz;
-                            memcpy(&hs, se, sizeof(hs));
-                            if (hs.l4_len == (uint32_t)d.l3_len - d.l4_off) hs.l4_len = (uint16_t)(take - d.l4_off);
-                            else hs.l2_len = 0;
-                            memcpy(se, &hs, sizeof(hs));
-                        }
+            // packet only its header (pre_staged_len; its descriptor's l3_len cut to that)
+            const int64_t pos = gather_blocks(
+                h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena, c->max_arena, [&](uint32_t i, const vpcsum_desc_t& d) {
+                    const uint8_t* e = (const uint8_t*)h_pre + (size_t)i * esz;
+                    bool cut;
+                    const uint32_t take = pre_staged_len(h_arena, d, e, pre_fmt, &cut);
+                    if (cut && (pre_entry_mask(e, pre_fmt) & VPCSUM_PRE_HSUM)) {
+                        // the kernel checks the record's segment length against the descriptor's,
+                        // which is cut here: check it against the real one on the host, and hand the
+                        // kernel the cut length (or, on a mismatch, a record it refuses)
+                        vpcsum_hsum_t hs;
+                        uint8_t* se = (uint8_t*)s.h_rw.p + (size_t)i * esz;
+                        memcpy(&hs, se, sizeof(hs));
+                        if (hs.l4_len == (uint32_t)d.l3_len - d.l4_off) hs.l4_len = (uint16_t)(take - d.l4_off);
+                        else hs.l2_len = 0;
+                        memcpy(se, &hs, sizeof(hs));
                     }
-                }
-                const uint64_t a0 = d.l3_off & ~(uint64_t)15;
-                const uint64_t a1 = std::min<uint64_t>((d.l3_off + take + 15) & ~(uint64_t)15, arena_len);
-                if (pos + (a1 - a0) > c->max_arena) return fail("vpcsum_ctx_submit_pre: gathered batch exceeds capacity");
-                memcpy(s.h_arena + pos, h_arena + a0, a1 - a0);
-                s.h_desc[i].l3_off = pos + (d.l3_off - a0);
-                pos += (a1 - a0 + 15) & ~(uint64_t)15;
-            }
-            VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
+                    return take;
+                });
+            if (pos < 0) return fail("vpcsum_ctx_submit_pre: gathered batch exceeds capacity");
+            VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
                       "H2D descriptors");
-            VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw, (size_t)n * esz, hipMemcpyHostToDevice, s.stream), "H2D pre-images");
+            VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw.p, (size_t)n * esz, hipMemcpyHostToDevice, s.stream), "H2D pre-images");
             if (pos) VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, pos, hipMemcpyHostToDevice, s.stream), "H2D frames");
             if (full)
                 VPC_CHECK(launch_csum(s.d_arena, pos, s.d_desc, n, s.d_out, s.d_status, nullptr, VPCSUM_MODE_COMPUTE, nullptr,
@@ -1379,23 +1303,10 @@ int vpcsum_ctx_submit_pre(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
             // the sums go back through out: slot_finish writes them into the caller's frames
             VPC_CHECK(launch_pre(s.d_arena, pos, s.d_desc, s.d_rw, (int)pre_fmt, n, s.d_out, s.d_status, 0, s.stream),
                       "pre-image launch");
-            VPC_CHECK(hipMemcpyAsync(s.h_out, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
-            VPC_CHECK(hipMemcpyAsync(s.h_status, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
-            s.zero_copy = false;
+            VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
+            VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
         }
-        VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
-        s.kind = 0;
-        s.svc_seq = 0;
-        s.busy = true;
-        s.ticket = t;
-        s.n = n;
-        s.mode = mode;
-        s.user_arena = h_arena;
-        s.user_desc = h_desc;
-        s.user_out = h_out;
-        s.user_status = h_status;
-        *ticket = t;
-        return 0;
+        return slot_commit(s, b, ticket);
     } VPC_CATCH("vpcsum_ctx_submit_pre")
 }
 
@@ -1405,7 +1316,7 @@ int vpcsum_ctx_wait(vpcsum_ctx_t* c, uint64_t ticket) {
         std::lock_guard<std::mutex> lk(c->mu);
         VPC_ON_DEVICE(c->device);
         Slot& s = c->slots[ticket & 1];
-        if (!s.busy || s.ticket != ticket) {
+        if (!s.busy || s.batch.ticket != ticket) {
             if (ticket == 0 || ticket >= c->next_ticket) return fail("vpcsum_ctx_wait: unknown ticket %llu", (unsigned long long)ticket);
             return 0;   // already completed
         }
@@ -1413,69 +1324,71 @@ int vpcsum_ctx_wait(vpcsum_ctx_t* c, uint64_t ticket) {
     } VPC_CATCH("vpcsum_ctx_wait")
 }
 
-// vpcsum_ctx_verify_frames / _hsum: h_hsum NULL = no header sums
-static int ctx_verify_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const uint64_t* h_frame_off,
-                             const uint32_t* h_frame_len, uint32_t n, uint32_t* h_out, uint8_t* h_status,
-                             vpcsum_hsum_t* h_hsum, uint64_t* ticket, const char* what) {
+}  // extern "C"
+
+// The shared start of the frame-table entries (verify, egress, parse): the arguments checked under
+// the entry's name (`also`: the array the entry needs besides the table; `nulls` names them all),
+// the registered arena's mapping, the next slot, and -- for a batch that is launched, not handed to
+// the service grid (`svc`) -- the frame table staged.  body(s, b, base, svc) then runs the batch
+// under c->mu on c's device; b carries the ticket and n, and is zero-copy.
+template <class Body>
+static int frames_entry(vpcsum_ctx* c, const char* what, const char* nulls, const uint8_t* h_arena, uint64_t arena_len,
+                        const uint64_t* h_frame_off, const uint32_t* h_frame_len, const void* also, uint32_t n,
+                        uint64_t* ticket, Body body) {
     if (!c || !ticket) return fail("%s: NULL context or ticket", what);
     if (n > c->max_pkts) return fail("%s: %u frames > capacity %u", what, n, c->max_pkts);
-    if (n && (!h_arena || !h_frame_off || !h_frame_len || !h_status))
-        return fail("%s: NULL arena, frame table or status", what);
+    if (n && (!h_arena || !h_frame_off || !h_frame_len || !also)) return fail("%s: NULL %s", what, nulls);
     std::lock_guard<std::mutex> lk(c->mu);
     VPC_ON_DEVICE(c->device);
     uint8_t* base = n ? mapped_dev(c, h_arena, arena_len) : nullptr;
     if (n && !base) return fail("%s: the arena must be registered (vpcsum_ctx_register_arena)", what);
-    const uint64_t t = c->next_ticket++;
-    Slot& s = c->slots[t & 1];
-    if (s.busy && slot_finish(c, s) != 0) return -1;
-    if (h_hsum && n && !s.h_hs) {
-        hipError_t e = hipHostMalloc((void**)&s.h_hs, (size_t)c->max_pkts * sizeof(vpcsum_hsum_t),
-                                     hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&s.dh_hs, s.h_hs, 0);
-        if (e != hipSuccess) {
-            if (s.h_hs) (void)hipHostFree(s.h_hs);
-            s.h_hs = s.dh_hs = nullptr;
-            return hipfail(e, what);
-        }
+    Batch b;
+    Slot* s = slot_acquire(c, &b.ticket);
+    if (!s) return -1;
+    b.n = n;
+    b.zero_copy = true;   // read, and written, in place through the mapping
+    const bool svc = n && c->svc.on && n <= kSvcBatchMax;
+    if (n && !svc) {
+        memcpy(s->h_foff.p, h_frame_off, (size_t)n * 8);
+        memcpy(s->h_flen.p, h_frame_len, (size_t)n * 4);
     }
-    if (n && c->svc.on && n <= kSvcBatchMax) {
+    return body(*s, b, base, svc);
+}
+
+extern "C" {
+
+// vpcsum_ctx_verify_frames / _hsum: h_hsum NULL = no header sums
+static int ctx_verify_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const uint64_t* h_frame_off,
+                             const uint32_t* h_frame_len, uint32_t n, uint32_t* h_out, uint8_t* h_status,
+                             vpcsum_hsum_t* h_hsum, uint64_t* ticket, const char* what) {
+    return frames_entry(c, what, "arena, frame table or status", h_arena, arena_len, h_frame_off, h_frame_len, h_status, n,
+                        ticket, [&](Slot& s, Batch b, uint8_t* base, bool svc) {
+        if (h_hsum && n && !s.h_hs.p) {
+            const hipError_t e = s.h_hs.alloc((size_t)c->max_pkts * sizeof(vpcsum_hsum_t));
+            if (e != hipSuccess) return hipfail(e, what);
+        }
+        b.mode = VPCSUM_MODE_VERIFY;
+        b.user_out = h_out;
+        b.user_status = h_status;
+        b.user_hsum = n ? h_hsum : nullptr;
         // a small received batch: the service grid parses and verifies each frame
         // (kernels.hip svc_frame_packet), the sums into its own buffer (copied out only with h_out),
         // the header sums into its aux buffer
-        if (svc_post_frames(c, s, t, h_arena, arena_len, base, h_frame_off, h_frame_len, nullptr, VPCSUM_F_IP | VPCSUM_F_L4,
-                            n, h_out, h_status, VPCSUM_MODE_VERIFY, false, ticket, h_hsum != nullptr) != 0)
-            return -1;
-        s.user_hsum = h_hsum;
-        return 0;
-    }
-    if (n) {
-        // parse the frames where they lie (zero-copy), then verify the descriptors it built
-        if (svc_quiesce(c) != 0) return -1;
-        memcpy(s.h_foff, h_frame_off, (size_t)n * 8);
-        memcpy(s.h_flen, h_frame_len, (size_t)n * 4);
-        VPC_CHECK(launch_parse_ether(base, arena_len, s.dh_foff, s.dh_flen, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
-                                     nullptr, nullptr, s.stream, nullptr, h_hsum ? s.dh_hs : nullptr),
-                  "parse launch");
-        // h_out NULL: the status bytes alone (the out words are 4 of the 5 result bytes a packet writes)
-        VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, h_out ? s.dh_out : nullptr, s.dh_status, nullptr,
-                              VPCSUM_MODE_VERIFY, nullptr, n <= kZeroCopyWaveTeams ? 12 : 0, 0, s.stream),
-                  "verify launch");
-    }
-    VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
-    s.zero_copy = true;
-    s.svc_seq = 0;
-    s.kind = 0;
-    s.busy = true;
-    s.ticket = t;
-    s.n = n;
-    s.mode = VPCSUM_MODE_VERIFY;
-    s.user_arena = nullptr;
-    s.user_desc = nullptr;
-    s.user_out = h_out;
-    s.user_status = h_status;
-    s.user_hsum = n ? h_hsum : nullptr;
-    *ticket = t;
-    return 0;
+        if (svc)
+            return svc_post_frames(c, s, b, arena_len, base, h_frame_off, h_frame_len, nullptr, VPCSUM_F_IP | VPCSUM_F_L4,
+                                   h_hsum ? kSvcHsum : 0, ticket);
+        if (n) {
+            // parse the frames where they lie (zero-copy), then verify the descriptors it built
+            VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
+                                         nullptr, nullptr, s.stream, nullptr, h_hsum ? s.h_hs.dev : nullptr),
+                      "parse launch");
+            // h_out NULL: the status bytes alone (the out words are 4 of the 5 result bytes a packet writes)
+            VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
+                                  VPCSUM_MODE_VERIFY, nullptr, zero_copy_variant(n), 0, s.stream),
+                      "verify launch");
+        }
+        return slot_commit(s, b, ticket);
+    });
 }
 
 int vpcsum_ctx_verify_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const uint64_t* h_frame_off,
@@ -1501,50 +1414,27 @@ int vpcsum_ctx_egress_frames(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_l
                              const uint32_t* h_frame_len, const uint8_t* h_frame_flags, uint32_t n, uint32_t* h_out,
                              uint8_t* h_status, uint64_t* ticket) {
     try {
-        if (!c || !ticket) return fail("vpcsum_ctx_egress_frames: NULL context or ticket");
-        if (n > c->max_pkts) return fail("vpcsum_ctx_egress_frames: %u frames > capacity %u", n, c->max_pkts);
-        if (n && (!h_arena || !h_frame_off || !h_frame_len || !h_frame_flags))
-            return fail("vpcsum_ctx_egress_frames: NULL arena, frame table or flags");
-        std::lock_guard<std::mutex> lk(c->mu);
-        VPC_ON_DEVICE(c->device);
-        uint8_t* base = n ? mapped_dev(c, h_arena, arena_len) : nullptr;
-        if (n && !base) return fail("vpcsum_ctx_egress_frames: the arena must be registered (vpcsum_ctx_register_arena)");
-        const uint64_t t = c->next_ticket++;
-        Slot& s = c->slots[t & 1];
-        if (s.busy && slot_finish(c, s) != 0) return -1;
-        if (n && c->svc.on && n <= kSvcBatchMax) {
+        return frames_entry(c, "vpcsum_ctx_egress_frames", "arena, frame table or flags", h_arena, arena_len, h_frame_off,
+                            h_frame_len, h_frame_flags, n, ticket, [&](Slot& s, Batch b, uint8_t* base, bool svc) {
+            b.mode = VPCSUM_MODE_WRITE;
+            b.user_out = h_out;
+            b.user_status = h_status;
             // a small flush: the service grid parses and sums each frame (kernels.hip svc_frame_packet)
-            return svc_post_frames(c, s, t, h_arena, arena_len, base, h_frame_off, h_frame_len, h_frame_flags, 0, n, h_out,
-                                   h_status, VPCSUM_MODE_WRITE, false, ticket);
-        }
-        if (n) {
-            if (svc_quiesce(c) != 0) return -1;
-            // the frames' own flags ride in the status staging: the parse reads them before the
-            // checksum kernel, later on the same stream, overwrites them with the statuses
-            memcpy(s.h_foff, h_frame_off, (size_t)n * 8);
-            memcpy(s.h_flen, h_frame_len, (size_t)n * 4);
-            memcpy(s.h_status, h_frame_flags, n);
-            VPC_CHECK(launch_parse_ether(base, arena_len, s.dh_foff, s.dh_flen, n, 0, s.d_desc, nullptr, nullptr, s.stream,
-                                         s.dh_status),
-                      "parse launch");
-            VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, s.dh_out, s.dh_status, nullptr, VPCSUM_MODE_COMPUTE, base,
-                                  n <= kZeroCopyWaveTeams ? 12 : 0, 0, s.stream),
-                      "checksum launch");
-        }
-        VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
-        s.zero_copy = true;
-        s.svc_seq = 0;
-        s.kind = 0;
-        s.busy = true;
-        s.ticket = t;
-        s.n = n;
-        s.mode = VPCSUM_MODE_WRITE;
-        s.user_arena = nullptr;   // written in place through the mapping
-        s.user_desc = nullptr;
-        s.user_out = h_out;
-        s.user_status = h_status;
-        *ticket = t;
-        return 0;
+            if (svc)
+                return svc_post_frames(c, s, b, arena_len, base, h_frame_off, h_frame_len, h_frame_flags, 0, 0, ticket);
+            if (n) {
+                // the frames' own flags ride in the status staging: the parse reads them before the
+                // checksum kernel, later on the same stream, overwrites them with the statuses
+                memcpy(s.h_status.p, h_frame_flags, n);
+                VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, 0, s.d_desc, nullptr, nullptr,
+                                             s.stream, s.h_status.dev),
+                          "parse launch");
+                VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, s.h_out.dev, s.h_status.dev, nullptr, VPCSUM_MODE_COMPUTE,
+                                      base, zero_copy_variant(n), 0, s.stream),
+                          "checksum launch");
+            }
+            return slot_commit(s, b, ticket);
+        });
     } VPC_CATCH("vpcsum_ctx_egress_frames")
 }
 
@@ -1552,61 +1442,28 @@ int vpcsum_ctx_parse_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t ar
                             const uint32_t* h_frame_len, uint32_t n, vpcsum_desc_t* h_desc, uint8_t* h_status,
                             vpcsum_tuple_t* h_tuples, uint64_t* ticket) {
     try {
-        if (!c || !ticket) return fail("vpcsum_ctx_parse_frames: NULL context or ticket");
-        if (n > c->max_pkts) return fail("vpcsum_ctx_parse_frames: %u frames > capacity %u", n, c->max_pkts);
-        if (n && (!h_arena || !h_frame_off || !h_frame_len)) return fail("vpcsum_ctx_parse_frames: NULL arena or frame table");
-        std::lock_guard<std::mutex> lk(c->mu);
-        VPC_ON_DEVICE(c->device);
-        uint8_t* base = n ? mapped_dev(c, h_arena, arena_len) : nullptr;
-        if (n && !base) return fail("vpcsum_ctx_parse_frames: the arena must be registered (vpcsum_ctx_register_arena)");
-        const uint64_t t = c->next_ticket++;
-        Slot& s = c->slots[t & 1];
-        if (s.busy && slot_finish(c, s) != 0) return -1;
-        if (!s.h_tu) {
-            hipError_t e = hipHostMalloc((void**)&s.h_tu, (size_t)c->max_pkts * sizeof(vpcsum_tuple_t),
-                                         hipHostMallocMapped | hipHostMallocCoherent);
-            if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&s.dh_tu, s.h_tu, 0);
-            if (e != hipSuccess) {
-                if (s.h_tu) (void)hipHostFree(s.h_tu);
-                s.h_tu = s.dh_tu = nullptr;
-                return hipfail(e, "vpcsum_ctx_parse_frames allocation");
+        return frames_entry(c, "vpcsum_ctx_parse_frames", "arena or frame table", h_arena, arena_len, h_frame_off,
+                            h_frame_len, h_arena, n, ticket, [&](Slot& s, Batch b, uint8_t* base, bool svc) {
+            if (!s.h_tu.p) {
+                const hipError_t e = s.h_tu.alloc((size_t)c->max_pkts * sizeof(vpcsum_tuple_t));
+                if (e != hipSuccess) return hipfail(e, "vpcsum_ctx_parse_frames allocation");
             }
-        }
-        if (n && c->svc.on && n <= kSvcBatchMax) {
+            b.kind = BatchKind::Parse;
+            b.user_status = h_status;
+            b.user_desc_out = h_desc;
+            b.user_tuples = h_tuples;
             // a small received batch: the service grid parses each frame (kernels.hip svc_frame_packet)
-            if (svc_post_frames(c, s, t, h_arena, arena_len, base, h_frame_off, h_frame_len, nullptr,
-                                VPCSUM_F_IP | VPCSUM_F_L4, n, nullptr, h_status, 0, true, ticket) != 0)
-                return -1;
-            s.kind = 2;
-            s.user_desc_out = h_desc;
-            s.user_tuples = h_tuples;
-            return 0;
-        }
-        if (n) {
-            // parsed where the frames lie (zero-copy); results straight into the pinned staging
-            if (svc_quiesce(c) != 0) return -1;
-            memcpy(s.h_foff, h_frame_off, (size_t)n * 8);
-            memcpy(s.h_flen, h_frame_len, (size_t)n * 4);
-            VPC_CHECK(launch_parse_ether(base, arena_len, s.dh_foff, s.dh_flen, n, VPCSUM_F_IP | VPCSUM_F_L4, s.dh_desc,
-                                         s.dh_status, s.dh_tu, s.stream),
-                      "parse launch");
-        }
-        VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
-        s.zero_copy = true;
-        s.svc_seq = 0;
-        s.kind = 2;
-        s.busy = true;
-        s.ticket = t;
-        s.n = n;
-        s.mode = 0;
-        s.user_arena = nullptr;
-        s.user_desc = nullptr;
-        s.user_out = nullptr;
-        s.user_status = h_status;
-        s.user_desc_out = h_desc;
-        s.user_tuples = h_tuples;
-        *ticket = t;
-        return 0;
+            if (svc)
+                return svc_post_frames(c, s, b, arena_len, base, h_frame_off, h_frame_len, nullptr, VPCSUM_F_IP | VPCSUM_F_L4,
+                                       kSvcParse, ticket);
+            if (n) {
+                // parsed where the frames lie (zero-copy); results straight into the pinned staging
+                VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4,
+                                             s.h_desc.dev, s.h_status.dev, s.h_tu.dev, s.stream),
+                          "parse launch");
+            }
+            return slot_commit(s, b, ticket);
+        });
     } VPC_CATCH("vpcsum_ctx_parse_frames")
 }
 
@@ -1619,68 +1476,43 @@ int vpcsum_ctx_nat_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
         if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | 0x100u)) return fail("vpcsum_ctx_nat_submit: bad nat_mode 0x%x", nat_mode);
         std::lock_guard<std::mutex> lk(c->mu);
         VPC_ON_DEVICE(c->device);
-        const uint64_t t = c->next_ticket++;
-        Slot& s = c->slots[t & 1];
-        if (s.busy && slot_finish(c, s) != 0) return -1;
+        Batch b;
+        Slot* slot = slot_acquire(c, &b.ticket);
+        if (!slot) return -1;
+        Slot& s = *slot;
+        b.kind = BatchKind::Nat;
+        b.n = n;
+        b.mode = nat_mode;
+        b.user_arena = h_arena;
+        b.user_desc = h_desc;
+        b.user_status = h_status;
         if (slot_rw_alloc(c, s, "vpcsum_ctx_nat_submit") != 0) return -1;
-        uint64_t lo = UINT64_MAX, hi = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            const vpcsum_desc_t& d = h_desc[i];
-            if (d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off) continue;   // the kernel flags it BAD
-            lo = std::min(lo, d.l3_off);
-            hi = std::max(hi, d.l3_off + d.l3_len);
-        }
-        if (lo == UINT64_MAX) { lo = 0; hi = 0; }
-        lo &= ~(uint64_t)15;
-        uint8_t* dev_arena = hi > lo ? mapped_dev(c, h_arena + lo, hi - lo) : nullptr;
-        memcpy(s.h_rw, h_rw, (size_t)n * sizeof(vpcsum_nat_t));
+        const BatchSpan sp = batch_span(h_desc, n, arena_len);
+        uint8_t* dev_arena = sp.hi > sp.lo ? mapped_dev(c, h_arena + sp.lo, sp.hi - sp.lo) : nullptr;
+        memcpy(s.h_rw.p, h_rw, (size_t)n * sizeof(vpcsum_nat_t));
         if (dev_arena) {
             // the frames live in a registered (page-locked, mapped) arena: rewritten where they lie
-            if (svc_quiesce(c) != 0) return -1;
-            memcpy(s.h_desc, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-            if (n && nat_run(dev_arena - lo, arena_len, s.dh_desc, s.dh_rw, 1, n, s.dh_status, nat_mode, s.stream) != 0)
+            memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+            if (n && nat_run(dev_arena - sp.lo, arena_len, s.h_desc.dev, s.h_rw.dev, 1, n, s.h_status.dev, nat_mode, s.stream) != 0)
                 return -1;
-            s.zero_copy = true;
+            b.zero_copy = true;
         } else {
             // staged: each packet's 16-B blocks gathered into the pinned staging, rewritten on the
             // device, and the whole gathered batch copied back (the headers return at wait)
-            uint64_t pos = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                const vpcsum_desc_t& d = h_desc[i];
-                s.h_desc[i] = d;
-                if (d.l3_off > arena_len || d.l3_len > arena_len - d.l3_off) { s.h_desc[i].l3_off = UINT64_MAX; continue; }
-                const uint64_t a0 = d.l3_off & ~(uint64_t)15;
-                const uint64_t a1 = std::min<uint64_t>((d.l3_off + d.l3_len + 15) & ~(uint64_t)15, arena_len);
-                if (pos + (a1 - a0) > c->max_arena) return fail("vpcsum_ctx_nat_submit: batch exceeds the staging capacity");
-                memcpy(s.h_arena + pos, h_arena + a0, a1 - a0);
-                s.h_desc[i].l3_off = pos + (d.l3_off - a0);
-                pos += (a1 - a0 + 15) & ~(uint64_t)15;
-            }
+            const int64_t pos = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena, c->max_arena);
+            if (pos < 0) return fail("vpcsum_ctx_nat_submit: batch exceeds the staging capacity");
             if (n) {
-                VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
+                VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
                           "H2D descriptors");
-                VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw, (size_t)n * sizeof(vpcsum_nat_t), hipMemcpyHostToDevice, s.stream),
+                VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw.p, (size_t)n * sizeof(vpcsum_nat_t), hipMemcpyHostToDevice, s.stream),
                           "H2D rewrites");
                 if (pos) VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, pos, hipMemcpyHostToDevice, s.stream), "H2D frames");
                 if (nat_run(s.d_arena, pos, s.d_desc, s.d_rw, 1, n, s.d_status, nat_mode, s.stream) != 0) return -1;
                 if (pos) VPC_CHECK(hipMemcpyAsync(s.h_arena, s.d_arena, pos, hipMemcpyDeviceToHost, s.stream), "D2H frames");
-                VPC_CHECK(hipMemcpyAsync(s.h_status, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
+                VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
             }
-            s.zero_copy = false;
         }
-        VPC_CHECK(hipEventRecord(s.done, s.stream), "hipEventRecord");
-        s.kind = 1;
-        s.svc_seq = 0;
-        s.busy = true;
-        s.ticket = t;
-        s.n = n;
-        s.mode = nat_mode;
-        s.user_arena = h_arena;
-        s.user_desc = h_desc;
-        s.user_out = nullptr;
-        s.user_status = h_status;
-        *ticket = t;
-        return 0;
+        return slot_commit(s, b, ticket);
     } VPC_CATCH("vpcsum_ctx_nat_submit")
 }
 
@@ -2136,17 +1968,34 @@ static int pni_throw(void* env, const char* type) {
     return -1;
 }
 
-int Java_io_vproxy_vpcsum_VPCsum_create(PNIEnv_vpcsum_long* env, int32_t device, int64_t maxArena, int32_t maxPkts) {
+}  // extern "C"
+
+// An entry point that returns a long (a ticket, a handle): `bad` arguments throw
+// IllegalArgumentException with bad_msg, a failed call(&value) IOException with the library's message.
+template <class Call>
+static int pni_returning(PNIEnv_vpcsum_long* env, const char* name, bool bad, const char* bad_msg, Call call) {
     try {
-        if (maxArena <= 0 || maxPkts <= 0) {
-            fail("maxArena and maxPkts must be positive");
+        if (bad) {
+            fail("%s", bad_msg);
             return pni_throw(env, "java.lang.IllegalArgumentException");
         }
-        vpcsum_ctx_t* c = nullptr;
-        if (vpcsum_ctx_create(device, (uint64_t)maxArena, (uint32_t)maxPkts, &c) != 0) return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)(intptr_t)c;
+        uint64_t value = 0;
+        if (call(&value) != 0) return pni_throw(env, "java.io.IOException");
+        env->return_ = (int64_t)value;
         return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_create")
+    } VPC_CATCH_PNI(name)
+}
+
+extern "C" {
+
+int Java_io_vproxy_vpcsum_VPCsum_create(PNIEnv_vpcsum_long* env, int32_t device, int64_t maxArena, int32_t maxPkts) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_create", maxArena <= 0 || maxPkts <= 0,
+                         "maxArena and maxPkts must be positive", [&](uint64_t* handle) {
+        vpcsum_ctx_t* c = nullptr;
+        const int rc = vpcsum_ctx_create(device, (uint64_t)maxArena, (uint32_t)maxPkts, &c);
+        *handle = (uint64_t)(uintptr_t)c;
+        return rc;
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_registerArena(PNIEnv_vpcsum_void* env, int64_t ctx, void* arena, int64_t len) {
@@ -2163,18 +2012,10 @@ int Java_io_vproxy_vpcsum_VPCsum_registerArena(PNIEnv_vpcsum_void* env, int64_t 
 
 int Java_io_vproxy_vpcsum_VPCsum_submit(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
                                         int32_t n, void* out, void* status, int32_t mode) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("negative length");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_submit((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen, (const vpcsum_desc_t*)desc,
-                              (uint32_t)n, (uint32_t*)out, (uint8_t*)status, (uint32_t)mode, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_submit")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_submit", n < 0 || arenaLen < 0, "negative length", [&](uint64_t* t) {
+        return vpcsum_ctx_submit((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen, (const vpcsum_desc_t*)desc,
+                                 (uint32_t)n, (uint32_t*)out, (uint8_t*)status, (uint32_t)mode, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_waitFor(PNIEnv_vpcsum_void* env, int64_t ctx, int64_t ticket) {
@@ -2186,107 +2027,65 @@ int Java_io_vproxy_vpcsum_VPCsum_waitFor(PNIEnv_vpcsum_void* env, int64_t ctx, i
 
 int Java_io_vproxy_vpcsum_VPCsum_verifyFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                               void* frameOff, void* frameLen, int32_t n, void* out, void* status) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("verifyFrames: negative size");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_verify_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
-                                     (const uint64_t*)frameOff, (const uint32_t*)frameLen, (uint32_t)n, (uint32_t*)out,
-                                     (uint8_t*)status, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_verifyFrames")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_verifyFrames", n < 0 || arenaLen < 0,
+                         "verifyFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_verify_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
+                                        (const uint64_t*)frameOff, (const uint32_t*)frameLen, (uint32_t)n, (uint32_t*)out,
+                                        (uint8_t*)status, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_verifyFramesHsum(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                                   void* frameOff, void* frameLen, int32_t n, void* out, void* status,
                                                   void* hsum) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("verifyFramesHsum: negative size");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_verify_frames_hsum((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
-                                          (const uint64_t*)frameOff, (const uint32_t*)frameLen, (uint32_t)n, (uint32_t*)out,
-                                          (uint8_t*)status, (vpcsum_hsum_t*)hsum, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_verifyFramesHsum")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_verifyFramesHsum", n < 0 || arenaLen < 0,
+                         "verifyFramesHsum: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_verify_frames_hsum((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
+                                             (const uint64_t*)frameOff, (const uint32_t*)frameLen, (uint32_t)n,
+                                             (uint32_t*)out, (uint8_t*)status, (vpcsum_hsum_t*)hsum, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_egressFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                               void* frameOff, void* frameLen, void* frameFlags, int32_t n, void* out,
                                               void* status) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("egressFrames: negative size");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_egress_frames((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
-                                     (const uint64_t*)frameOff, (const uint32_t*)frameLen, (const uint8_t*)frameFlags,
-                                     (uint32_t)n, (uint32_t*)out, (uint8_t*)status, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_egressFrames")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_egressFrames", n < 0 || arenaLen < 0,
+                         "egressFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_egress_frames((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
+                                        (const uint64_t*)frameOff, (const uint32_t*)frameLen, (const uint8_t*)frameFlags,
+                                        (uint32_t)n, (uint32_t*)out, (uint8_t*)status, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_parseFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                              void* frameOff, void* frameLen, int32_t n, void* desc, void* status,
                                              void* tuples) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("parseFrames: negative size");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_parse_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
-                                    (const uint64_t*)frameOff, (const uint32_t*)frameLen, (uint32_t)n,
-                                    (vpcsum_desc_t*)desc, (uint8_t*)status, (vpcsum_tuple_t*)tuples, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_parseFrames")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_parseFrames", n < 0 || arenaLen < 0,
+                         "parseFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_parse_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
+                                       (const uint64_t*)frameOff, (const uint32_t*)frameLen, (uint32_t)n,
+                                       (vpcsum_desc_t*)desc, (uint8_t*)status, (vpcsum_tuple_t*)tuples, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_submitPre(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                            void* desc, void* pre, int32_t n, void* out, void* status, int32_t mode) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("submitPre: negative size");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_submit_pre((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
-                                  (const vpcsum_desc_t*)desc, pre, VPCSUM_PRE_FMT_PRE, (uint32_t)n, (uint32_t*)out,
-                                  (uint8_t*)status, (uint32_t)mode, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_submitPre")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_submitPre", n < 0 || arenaLen < 0, "submitPre: negative size",
+                         [&](uint64_t* t) {
+        return vpcsum_ctx_submit_pre((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
+                                     (const vpcsum_desc_t*)desc, pre, VPCSUM_PRE_FMT_PRE, (uint32_t)n, (uint32_t*)out,
+                                     (uint8_t*)status, (uint32_t)mode, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_natSubmit(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                            void* desc, void* rw, int32_t n, void* status, int32_t natMode) {
-    try {
-        if (n < 0 || arenaLen < 0) {
-            fail("natSubmit: negative size");
-            return pni_throw(env, "java.lang.IllegalArgumentException");
-        }
-        uint64_t t = 0;
-        if (vpcsum_ctx_nat_submit((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
-                                  (const vpcsum_desc_t*)desc, (const vpcsum_nat_t*)rw, (uint32_t)n, (uint8_t*)status,
-                                  (uint32_t)natMode, &t) != 0)
-            return pni_throw(env, "java.io.IOException");
-        env->return_ = (int64_t)t;
-        return 0;
-    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_natSubmit")
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_natSubmit", n < 0 || arenaLen < 0, "natSubmit: negative size",
+                         [&](uint64_t* t) {
+        return vpcsum_ctx_nat_submit((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
+                                     (const vpcsum_desc_t*)desc, (const vpcsum_nat_t*)rw, (uint32_t)n, (uint8_t*)status,
+                                     (uint32_t)natMode, t);
+    });
 }
 
 int Java_io_vproxy_vpcsum_VPCsum_setService(PNIEnv_vpcsum_void* env, int64_t ctx, int32_t idleUs) {

@@ -64,7 +64,7 @@ constexpr uint32_t kSvcMaxPkts = (1u << 23) - 1;   // the command's n field (bit
 constexpr uint32_t kSvcBatchMax = 512;              // largest batch the host hands to the service (api.cpp)
 constexpr int kServiceGrid = 32;   // workgroups: 4 waves each, one packet per wave and round (default)
 hipError_t launch_service(SvcMailbox* d_mb, uint32_t* d_ctr, uint32_t seen, uint64_t idle_ticks, hipStream_t stream,
-                          uint32_t grid = kServiceGrid, uint32_t poll = 0);
+                          uint32_t grid, uint32_t poll);
 // Tooling: a resident grid of `wgs` workgroups x `threads` that only sleeps (s_sleep) for `ticks`
 // (100 MHz) -- no memory traffic: the control for "a resident kernel on another queue" A/Bs.
 hipError_t launch_spin_probe(uint32_t wgs, uint32_t threads, uint64_t ticks, hipStream_t stream);
