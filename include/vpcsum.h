@@ -44,7 +44,10 @@ extern "C" {
  * 4 (round 6): the ingress header sum (vpcsum_hsum_t, VPCSUM_PRE_HSUM entries;
  * vpcsum_ctx_verify_frames_hsum, vpcsum_parse_ether_hsum_async, VPCsum.verifyFramesHsum): the
  * egress pre-image flush no longer depends on which setters ran; vpcsum_ctx_submit stages memory
- * the context has not registered instead of copying from it directly. */
+ * the context has not registered instead of copying from it directly.
+ * Additive since (the version stays 4): VPCSUM_NAT_TCP entries under the nat_mode bit
+ * VPCSUM_NAT_TCP_REWRITES; a library from before answers that bit with "bad nat_mode", which is
+ * how a caller probes for it. */
 #define VPCSUM_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -94,6 +97,11 @@ typedef struct vpcsum_desc {
 #define VPCSUM_S_IP_OK       0x01u /* verify: stored IPv4 header checksum == recomputed   */
 #define VPCSUM_S_L4_OK       0x02u /* verify: stored L4 checksum == recomputed            */
 #define VPCSUM_S_UDP_NOCSUM  0x04u /* UDP with stored checksum 0 (RFC 768 "no checksum")  */
+#define VPCSUM_S_MSS_ABSENT  0x08u /* NAT with VPCSUM_NAT_TCP_REWRITES, next to S_DONE:
+                                    * VPCSUM_TCP_CLAMP_MSS on a SYN whose options parse and hold no
+                                    * MSS option.  The packet is otherwise complete; the caller adds
+                                    * the option on the host (checkAndUpdateMss's rebuild branch,
+                                    * SwitchUtils.java:83-94: it changes lengths)                  */
 #define VPCSUM_S_TTL_EXPIRED 0x20u /* NAT: VPCSUM_NAT_DEC_TTL on a TTL / hop limit <= 1 (the value
                                     * after VPCSUM_NAT_SET_TTL when both are set): the packet is
                                     * refused with S_BAD_DESC and nothing is written.  The reference
@@ -120,6 +128,29 @@ typedef struct vpcsum_desc {
 #define VPCSUM_NAT_DEC_TTL  0x10u /* IPv4 TTL / IPv6 hop limit minus 1 (after SET_TTL if both); a
                                    * value <= 1 refuses the packet (VPCSUM_S_TTL_EXPIRED)        */
 #define VPCSUM_NAT_SET_TTL  0x20u /* IPv4 TTL / IPv6 hop limit := the entry's ttl value           */
+#define VPCSUM_NAT_TCP      0x40u /* vpcsum_nat_t only, honoured only under the nat_mode bit
+                                   * VPCSUM_NAT_TCP_REWRITES: rsv[0..7] hold TCP-header rewrites   */
+
+/* The TCP part of a vpcsum_nat_t entry with VPCSUM_NAT_TCP -- what the reference does to a NAT'd
+ * TCP packet in place besides applyNat: buildSynPacketForProxyProtocol (SwitchUtils.java:461-465,
+ * setSeqNum(seq - N)), buildSynAckPacketForProxyProtocol (:467-473, setSeqNum(seq - 1),
+ * setFlags(SYN|ACK)) and checkAndUpdateMss (:46-95, run by every Switch.sendPacket).
+ *   rsv[0]     ops, VPCSUM_TCP_*
+ *   rsv[1]     the flags value (low 6 bits; TcpPacket.setFlags, TcpPacket.java:90-96)
+ *   rsv[2..3]  maxMss, network order
+ *   rsv[4..7]  the sequence addend, network order, added mod 2^32 (seq - N: the addend -N)
+ *   rsv[8..9]  0
+ * Applied after the address / port / TTL rewrite, to a packet that rewrite did not refuse, with
+ * l4_proto 6 and 20 bytes of segment; any other packet ignores the ops (as SPORT / DPORT on ICMP).
+ * SET_FLAGS and SEQ_ADD always dirty the TCP sum (the setters call checksumSkipped() whatever the
+ * value).  CLAMP_MSS applies when SYN is set after SET_FLAGS: the options are walked as
+ * TcpPacket.from walks them (TcpPacket.java:241-287, TcpOption.check :622-636); a walk that fails
+ * changes nothing (Java's ensurePartialPacketParsed returns); else the first MSS option before any
+ * END has its 2 data bytes overwritten when its value is above maxMss (sum dirtied), is left
+ * alone when not (nothing dirtied), and when there is none VPCSUM_S_MSS_ABSENT is set. */
+#define VPCSUM_TCP_SEQ_ADD   0x01u
+#define VPCSUM_TCP_SET_FLAGS 0x02u
+#define VPCSUM_TCP_CLAMP_MSS 0x04u
 
 /* IPv4-only entry, 16 bytes (BASELINE config C5: 72 algorithmic bytes per packet).
  * rsv[0] carries the VPCSUM_NAT_SET_TTL value; an IPv6 descriptor is rejected (S_BAD_DESC). */
@@ -140,7 +171,7 @@ typedef struct vpcsum_nat {
     uint8_t  dport[2];
     uint8_t  mask;     /* VPCSUM_NAT_*                                  */
     uint8_t  ttl;      /* TTL / hop limit value for VPCSUM_NAT_SET_TTL    */
-    uint8_t  rsv[10];  /* 0                                             */
+    uint8_t  rsv[10];  /* 0, or with VPCSUM_NAT_TCP the TCP rewrites above */
 } vpcsum_nat_t;
 
 /* IPv4 record, 32 bytes: a packet's descriptor and its IPv4 entry side by side, so the rewrite
@@ -154,6 +185,13 @@ typedef struct vpcsum_nat4_rec {
 #define VPCSUM_NAT_RFC1624     0x00u /* incremental update (RFC 1624 eqn. 3); header bytes only */
 #define VPCSUM_NAT_STRICT_JAVA 0x01u /* rewrite, then full recompute: identical to Java for ANY
                                         input, including invalid input checksums              */
+#define VPCSUM_NAT_TCP_REWRITES 0x02u /* honour VPCSUM_NAT_TCP in this batch (48-byte entries only,
+                                        * a status buffer required).  Without it the mask bit and
+                                        * rsv are ignored and the kernels launched are unchanged.
+                                        * RFC 1624: the TCP sum is updated over the changed words,
+                                        * composed with the address / port update.  Strict Java: the
+                                        * rewrite adds F_L4 to the packet's dirty flags before the
+                                        * recompute; S_MSS_ABSENT is derived from the bytes after it */
 
 /* Pre-image of a packet NAT'd by Java's own setters (VPCSUM_F_PRE): the OLD addresses and ports,
  * recorded just before SwitchUtils.applyNat ran the setters (SwitchUtils.java:531-542), in the
@@ -234,7 +272,9 @@ int vpcsum_pipe_destroy(vpcsum_pipe_t* pipe);
 
 /* NAT / TTL rewrite + checksum update, in place in the arena; d_rw[i] rewrites packet i.
  * d_status (n bytes): S_DONE, or S_BAD_DESC for a rejected descriptor (nothing written);
- * required with VPCSUM_NAT_STRICT_JAVA. */
+ * required with VPCSUM_NAT_STRICT_JAVA and with VPCSUM_NAT_TCP_REWRITES.  That mode bit is taken
+ * by vpcsum_nat_async (and the host-frame submits built on it) only: the 16-byte entry formats
+ * refuse it. */
 int vpcsum_nat4_async(uint8_t* d_arena, uint64_t arena_len,
                       const vpcsum_desc_t* d_desc, const vpcsum_nat4_t* d_rw, uint32_t n,
                       uint8_t* d_status, uint32_t nat_mode, void* stream);
@@ -427,8 +467,10 @@ int vpcsum_ctx_egress_frames(vpcsum_ctx_t* ctx, uint8_t* h_arena, uint64_t arena
  * packet of h_desc[i] in place in the caller's frames, with the checksums updated as Java's
  * recompute leaves them (nat_mode as vpcsum_nat_async).  Frames in a registered arena are
  * rewritten where they lie (zero-copy); others are staged to the device and their rewritten
- * header bytes (L3 header through the L4 checksum field) copied back at vpcsum_ctx_wait.
- * h_status (may be NULL): S_DONE / S_BAD_DESC per packet.  Frames of one batch must not overlap. */
+ * header bytes (L3 header through the L4 checksum field; with VPCSUM_NAT_TCP_REWRITES the TCP
+ * header too) copied back at vpcsum_ctx_wait.
+ * h_status (may be NULL, but not with VPCSUM_NAT_TCP_REWRITES: S_MSS_ABSENT is the caller's to
+ * act on): S_DONE / S_BAD_DESC per packet.  Frames of one batch must not overlap. */
 int vpcsum_ctx_nat_submit(vpcsum_ctx_t* ctx, uint8_t* h_arena, uint64_t arena_len,
                           const vpcsum_desc_t* h_desc, const vpcsum_nat_t* h_rw, uint32_t n,
                           uint8_t* h_status, uint32_t nat_mode, uint64_t* ticket);

@@ -350,6 +350,21 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * {@link #nat} with the TCP-header rewrites of the entries that carry VPCsum.NAT_TCP
+     * (VPCsum.natTcp: PROXY-protocol sequence addend and flags, checkAndUpdateMss's clamp) honoured:
+     * the batch runs with VPCsum.NAT_TCP_REWRITES.  A status byte with VPCsum.S_MSS_ABSENT is a SYN
+     * without an MSS option: the caller adds it on the host (SwitchUtils.java:83-94).  Throws the
+     * library's "bad nat_mode" when the loaded library is from before the feature.
+     */
+    public MemorySegment natTcp(MemorySegment natDesc, MemorySegment rw, int count, boolean strictJava,
+                                MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().natSubmit(env, ctx, umem, umemLen, natDesc, rw, count, statusOut,
+            (strictJava ? VPCsum.NAT_STRICT_JAVA : VPCsum.NAT_RFC1624) | VPCsum.NAT_TCP_REWRITES);
+        VPCsum.get().waitFor(env, ctx, t);
+        return statusOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

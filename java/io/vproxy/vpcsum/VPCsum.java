@@ -86,6 +86,40 @@ public class VPCsum {
     public static final int NAT_STRICT_JAVA = 0x01;
     /** bytes of one vpcsum_nat_t rewrite entry: src[16] dst[16] sport[2] dport[2] mask ttl rsv[10] */
     public static final int NAT_ENTRY = 48;
+    /** natMode bit: honour {@link #NAT_TCP} entries in this batch (a status segment is required).  A
+     * library from before the feature throws "bad nat_mode": that refusal is the probe. */
+    public static final int NAT_TCP_REWRITES = 0x02;
+    /** vpcsum_nat_t.mask bit: rsv[0..7] hold TCP-header rewrites ({@link #natTcp}) -- what the
+     * reference does to a NAT'd TCP packet besides applyNat: buildSynPacketForProxyProtocol
+     * (SwitchUtils.java:461-465), buildSynAckPacketForProxyProtocol (:467-473), checkAndUpdateMss
+     * (:46-95).  Ignored without {@link #NAT_TCP_REWRITES}. */
+    public static final int NAT_TCP = 0x40;
+    public static final int TCP_SEQ_ADD = 0x01;
+    public static final int TCP_SET_FLAGS = 0x02;
+    public static final int TCP_CLAMP_MSS = 0x04;
+    /** NAT with NAT_TCP_REWRITES, next to S_DONE: TCP_CLAMP_MSS on a SYN whose options parse and hold
+     * no MSS option.  The packet is otherwise done; add the option on the host (checkAndUpdateMss's
+     * rebuild branch, SwitchUtils.java:83-94) and flush that frame in full. */
+    public static final int S_MSS_ABSENT = 0x08;
+
+    /** Fill the TCP part of the 48-byte entry at {@code rw[off..]}: {@code ops} TCP_*, {@code flags}
+     * the new TCP flags (low 6 bits, TcpPacket.setFlags), {@code maxMss} the egress port's clamp,
+     * {@code seqAdd} added to the sequence number mod 2^32 (seq - N: pass -N).  setSeqNum and setFlags
+     * dirty the TCP sum whatever the value; the clamp only when it writes. */
+    public static void natTcp(MemorySegment rw, long off, int ops, int flags, int maxMss, int seqAdd) {
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 36,
+            (byte) (rw.get(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 36) | NAT_TCP));
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 38, (byte) ops);
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 39, (byte) (flags & 0x3f));
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 40, (byte) (maxMss >> 8));
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 41, (byte) maxMss);
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 42, (byte) (seqAdd >> 24));
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 43, (byte) (seqAdd >> 16));
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 44, (byte) (seqAdd >> 8));
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 45, (byte) seqAdd);
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 46, (byte) 0);
+        rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 47, (byte) 0);
+    }
 
     private static final MethodHandle createMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
         "Java_io_vproxy_vpcsum_VPCsum_create", int.class /* device */, long.class /* maxArena */, int.class /* maxPkts */);
@@ -314,7 +348,9 @@ public class VPCsum {
      * (48-byte vpcsum_nat_t entries: addresses, ports, TTL / hop limit) into the packet of
      * {@code desc[i]} in place, with the checksums updated as getRawPacket(0) would recompute them
      * (NAT_RFC1624 on valid input, NAT_STRICT_JAVA for any input).  Frames in the registered umem
-     * are rewritten where they lie.  status[i]: S_DONE or S_BAD_DESC.  Returns a ticket for
+     * are rewritten where they lie.  status[i]: S_DONE or S_BAD_DESC.  With NAT_TCP_REWRITES in
+     * natMode, entries with NAT_TCP also rewrite the sequence number, the flags and the MSS option
+     * ({@link #natTcp}); status[i] may then carry S_MSS_ABSENT.  Returns a ticket for
      * {@link #waitFor}. */
     public long natSubmit(PNIEnv ENV, long ctx, MemorySegment arena, long arenaLen, MemorySegment desc,
                           MemorySegment rw, int n, MemorySegment status, int natMode) throws java.io.IOException {

@@ -35,6 +35,54 @@ if "--probe" in sys.argv:   # the pattern ceiling and the bench's form (no statu
             torch.cuda.synchronize()
             ms = e0.elapsed_ms(e1) / 10
             res.setdefault(name, []).append({"ms": round(ms, 4), "Mpps": round(n / ms / 1e3, 1)})
+if "--tcp" in sys.argv:
+    # The price of the TCP-header pass (VPCSUM_NAT_TCP_REWRITES): 48-B entries on the C5 batch, RFC
+    # 1624, three legs in alternating rounds of one call so that drift hits them alike:
+    #   a  no mode bit (the kernels launched are the ones from before the feature)
+    #   b  the mode bit, no entry carrying VPCSUM_NAT_TCP (the extra pass reads 4 B per entry)
+    #   c  the mode bit, 1 in 16 TCP packets with SEQ_ADD | SET_FLAGS | CLAMP_MSS
+    # A library from before the feature refuses the mode bit ("bad nat_mode"): a alone is measured.
+    g_ = torch.Generator(device="cpu").manual_seed(6)
+    r48 = torch.zeros((n, 48), dtype=torch.uint8)
+    r48[:, :36] = torch.randint(0, 256, (n, 36), dtype=torch.uint8, generator=g_)
+    r48[:, 36] = V.NAT_SRC | V.NAT_DST | V.NAT_SPORT | V.NAT_DPORT
+    tcp_idx = torch.nonzero(d.view(n, 16)[:, 13].cpu() == 6).flatten()[::16]
+    r48c = r48.clone()
+    r48c[tcp_idx, 36] |= 0x40                                  # VPCSUM_NAT_TCP
+    r48c[tcp_idx, 38] = 0x01 | 0x02 | 0x04                     # SEQ_ADD | SET_FLAGS | CLAMP_MSS
+    r48c[tcp_idx, 39] = 0x12                                   # SYN | ACK
+    r48c[tcp_idx, 40:42] = torch.tensor([0x05, 0x78], dtype=torch.uint8)          # maxMss 1400
+    r48c[tcp_idx, 42:46] = torch.tensor([0xFF, 0xFF, 0xFF, 0xFF], dtype=torch.uint8)   # seq - 1
+    r48, r48c = r48.cuda(), r48c.cuda()
+    TCP_REWRITES = 0x02
+    legs = [("a_no_mode_bit", r48, V.NAT_RFC1624), ("b_mode_bit_no_tcp_entries", r48, V.NAT_RFC1624 | TCP_REWRITES),
+            ("c_mode_bit_1_in_16_tcp", r48c, V.NAT_RFC1624 | TCP_REWRITES)]
+    try:
+        V.nat(arena, d, r48, n, st, V.NAT_RFC1624 | TCP_REWRITES)
+    except V.VpcsumError as e:
+        res["mode_bit"] = f"refused by this library ({e})"
+        legs = legs[:1]
+    out = {name: [] for name, _, _ in legs}
+    for rnd in range(7):
+        for name, ent, mode in legs:
+            for _ in range(3):
+                V.nat(arena, d, ent, n, st, mode)
+            e0, e1 = V.Event(), V.Event()
+            e0.record()
+            for _ in range(10):
+                V.nat(arena, d, ent, n, st, mode)
+            e1.record()
+            torch.cuda.synchronize()
+            out[name].append(round(n / (e0.elapsed_ms(e1) / 10) / 1e3, 1))
+    assert int((st & V.S_BAD_DESC).sum().item()) == 0
+    res["tcp"] = {name: {"Mpps_rounds": v, "Mpps_median": sorted(v)[len(v) // 2], "Mpps_min": min(v), "Mpps_max": max(v)}
+                  for name, v in out.items()}
+    res["tcp"]["tcp_entries_in_c"] = int(tcp_idx.numel())
+    res["tcp"]["note"] = ("C5 frames carry no TCP options: CLAMP_MSS walks nothing; every rewritten packet becomes a "
+                          "SYN|ACK without an MSS option and reports S_MSS_ABSENT")
+    print(json.dumps(res))
+    sys.exit(0)
+
 for name, mode in modes:
     for _ in range(3):
         V.nat4(arena, d, rw, n, st, mode)

@@ -444,18 +444,25 @@ int vpcsum_pipe_destroy(vpcsum_pipe_t* p) {
 // dirtied, written in place -- Java's getRawPacket(0) after the setters.
 static int nat_run(uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, const void* d_rw, int fmt,
                    uint32_t n, uint8_t* d_status, uint32_t nat_mode, hipStream_t s) {
+    // VPCSUM_NAT_TCP_REWRITES (48-B entries, a status buffer: the callers' checks): the TCP-header
+    // rewrites of VPCSUM_NAT_TCP entries, a pass of their own after the rewrite
+    const bool tcp = (nat_mode & VPCSUM_NAT_TCP_REWRITES) != 0;
     if (nat_mode & VPCSUM_NAT_STRICT_JAVA) {
         // pass 1: rewrite fields, record which sums went dirty (Java's checksumSkipped())
         VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, fmt, n, nullptr, d_status, nat_mode, s), "nat launch");
+        if (tcp) VPC_CHECK(launch_nat_tcp(d_arena, arena_len, d_desc, d_rw, n, d_status, 1, s), "nat tcp launch");
         // pass 2: full recompute of the dirty sums, written in place (getRawPacket(0))
         VPC_CHECK(launch_csum(d_arena, arena_len, d_desc, n, nullptr, d_status, d_status, VPCSUM_MODE_WRITE, d_arena,
                               0, 0, s),
                   "nat recompute launch");
         // pass 3: the TTL-expired packets (refused, untouched) get S_TTL_EXPIRED next to S_BAD_DESC
         VPC_CHECK(launch_nat_ttl_status(d_arena, arena_len, d_desc, d_rw, fmt, n, d_status, s), "nat ttl status launch");
+        // and the SYNs a clamp found without an MSS option S_MSS_ABSENT next to S_DONE
+        if (tcp) VPC_CHECK(launch_nat_tcp(d_arena, arena_len, d_desc, d_rw, n, d_status, 2, s), "nat tcp status launch");
         return 0;
     }
     VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, fmt, n, d_status, nullptr, nat_mode, s), "nat launch");
+    if (tcp) VPC_CHECK(launch_nat_tcp(d_arena, arena_len, d_desc, d_rw, n, d_status, 0, s), "nat tcp launch");
     return 0;
 }
 
@@ -467,7 +474,11 @@ static int nat_async(const char* what, uint8_t* d_arena, uint64_t arena_len, con
     // kernel, bits 12..14 packets per lane of the wide kernel (the quad kernel clamps 4 to 2), bits
     // 16..17 window chunks, bits 18..22 workgroups per CU, bit 23 the lane layout of the wide kernel
     // instead of quads, bits 24..25 the quad kernel's forced occupancy (6 / 8 waves: may spill)
-    if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | 0x100u | 0x7000u | 0x3ff0000u)) return fail("%s: bad nat_mode 0x%x", what, nat_mode);
+    if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | VPCSUM_NAT_TCP_REWRITES | 0x100u | 0x7000u | 0x3ff0000u))
+        return fail("%s: bad nat_mode 0x%x", what, nat_mode);
+    if ((nat_mode & VPCSUM_NAT_TCP_REWRITES) && fmt != 1)
+        return fail("%s: VPCSUM_NAT_TCP_REWRITES takes 48-byte vpcsum_nat_t entries only (vpcsum_nat_async)", what);
+    if ((nat_mode & VPCSUM_NAT_TCP_REWRITES) && !d_status) return fail("%s: VPCSUM_NAT_TCP_REWRITES needs a status buffer", what);
     if ((nat_mode & VPCSUM_NAT_STRICT_JAVA) && !d_status) return fail("%s: strict-java mode needs a status buffer", what);
     if ((nat_mode & VPCSUM_NAT_STRICT_JAVA) && fmt == 2) return fail("%s: records take VPCSUM_NAT_RFC1624 only", what);
     return nat_run(d_arena, arena_len, d_desc, d_rw, fmt, n, d_status, nat_mode, (hipStream_t)stream);
@@ -960,13 +971,16 @@ static int slot_finish(vpcsum_ctx* c, Slot& s) {
     if (b.user_status) memcpy(b.user_status, res_status, b.n);
     switch (b.kind) {
     case BatchKind::Nat:
-        // a staged batch's rewritten headers (L3 header through the L4 checksum field) go back
-        // into the caller's frames; zero-copy batches rewrote them in place
+        // a staged batch's rewritten headers (L3 header through the L4 checksum field; the TCP
+        // header too under VPCSUM_NAT_TCP_REWRITES) go back into the caller's frames; zero-copy
+        // batches rewrote them in place
         if (!b.zero_copy && b.user_arena) {
+            const bool tcp = (b.mode & VPCSUM_NAT_TCP_REWRITES) != 0;
             for (uint32_t i = 0; i < b.n; ++i) {
                 if (res_status[i] & VPCSUM_S_BAD_DESC) continue;
                 const vpcsum_desc_t& d = b.user_desc[i];
-                memcpy(b.user_arena + d.l3_off, s.h_arena + s.h_desc.p[i].l3_off, nat_header_end(d));
+                memcpy(b.user_arena + d.l3_off, s.h_arena + s.h_desc.p[i].l3_off,
+                       tcp ? nat_tcp_header_end(d) : nat_header_end(d));
             }
         }
         break;
@@ -1473,7 +1487,11 @@ int vpcsum_ctx_nat_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
         if (!c || !ticket) return fail("vpcsum_ctx_nat_submit: NULL context or ticket");
         if (n > c->max_pkts) return fail("vpcsum_ctx_nat_submit: %u packets > capacity %u", n, c->max_pkts);
         if (n && (!h_arena || !h_desc || !h_rw)) return fail("vpcsum_ctx_nat_submit: NULL arena, descriptors or rewrites");
-        if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | 0x100u)) return fail("vpcsum_ctx_nat_submit: bad nat_mode 0x%x", nat_mode);
+        if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | VPCSUM_NAT_TCP_REWRITES | 0x100u))
+            return fail("vpcsum_ctx_nat_submit: bad nat_mode 0x%x", nat_mode);
+        // without the status bytes the caller would never see S_MSS_ABSENT, its part of the clamp
+        if ((nat_mode & VPCSUM_NAT_TCP_REWRITES) && !h_status)
+            return fail("vpcsum_ctx_nat_submit: VPCSUM_NAT_TCP_REWRITES needs a status buffer");
         std::lock_guard<std::mutex> lk(c->mu);
         VPC_ON_DEVICE(c->device);
         Batch b;

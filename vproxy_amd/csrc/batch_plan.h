@@ -79,6 +79,15 @@ inline uint32_t nat_header_end(const vpcsum_desc_t& d) {
     return std::min<uint32_t>(end, d.l3_len);
 }
 
+// The same under VPCSUM_NAT_TCP_REWRITES: a TCP packet with its 20-byte header in the segment can
+// also change in its sequence number, flags and options, so its whole TCP header goes back, taken
+// at the longest a data offset allows (60 bytes; the bytes past the real header return unchanged).
+inline uint32_t nat_tcp_header_end(const vpcsum_desc_t& d) {
+    if (d.l4_proto == 6 && d.l3_len >= d.l4_off + 20u)
+        return std::max<uint32_t>(nat_header_end(d), std::min<uint32_t>(d.l4_off + 60u, d.l3_len));
+    return nat_header_end(d);
+}
+
 // The mask byte of a pre-image entry (vpcsum_pre_t / vpcsum_pre4_t).
 inline uint8_t pre_entry_mask(const void* entry, uint32_t pre_fmt) {
     return ((const uint8_t*)entry)[pre_fmt == VPCSUM_PRE_FMT_PRE ? offsetof(vpcsum_pre_t, mask) : offsetof(vpcsum_pre4_t, mask)];

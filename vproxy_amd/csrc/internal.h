@@ -83,6 +83,11 @@ hipError_t launch_pre(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* d
 // strict mode, after the recompute: S_TTL_EXPIRED on the packets refused for their TTL
 hipError_t launch_nat_ttl_status(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw,
                                  int fmt, uint32_t n, uint8_t* status, hipStream_t stream);
+// the TCP-header rewrites of VPCSUM_NAT_TCP entries (vpcsum_nat_t, VPCSUM_NAT_TCP_REWRITES), after
+// launch_nat on the same stream.  phase 0: RFC 1624, res = the status; 1: strict, res = the dirty
+// flags, before the recompute; 2: strict, res = the status after it (S_MSS_ABSENT)
+hipError_t launch_nat_tcp(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, uint32_t n,
+                          uint8_t* res, int phase, hipStream_t stream);
 
 hipError_t launch_parse_ether(const uint8_t* arena, uint64_t arena_len, const uint64_t* frame_off,
                               const uint32_t* frame_len, uint32_t n, uint8_t flags, vpcsum_desc_t* desc,

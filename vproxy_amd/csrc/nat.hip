@@ -18,6 +18,8 @@
 // vpcsum_nat_t (48 B, IPv4 and IPv6), and vpcsum_nat4_rec_t (FMT 2: the descriptor and the IPv4
 // entry in one 32-B record, so a packet's rewrite comes from one read stream instead of two).  One lane per packet for the rewrite; the default wide
 // kernel (k_natq) moves the header windows in and out by quads of lanes.
+// Under VPCSUM_NAT_TCP_REWRITES a second pass (k_nat_tcp, tcp_rewrite.h) applies the TCP-header
+// rewrites of the 48-B entries that carry VPCSUM_NAT_TCP: sequence addend, flags, MSS clamp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -25,6 +27,7 @@
 #include "internal.h"
 #include "device_common.h"
 #include "pre_common.h"
+#include "tcp_rewrite.h"
 
 namespace vpcsum {
 
@@ -830,6 +833,72 @@ hipError_t launch_nat_ttl_status(const uint8_t* arena, uint64_t arena_len, const
         hipLaunchKernelGGL(k_nat_ttl_status<0>, dim3(g), dim3(256), 0, stream, arena, arena_len, (const uint4*)desc, rw, n, status);
     else
         hipLaunchKernelGGL(k_nat_ttl_status<1>, dim3(g), dim3(256), 0, stream, arena, arena_len, (const uint4*)desc, rw, n, status);
+    return hipGetLastError();
+}
+
+// The TCP-header rewrites of VPCSUM_NAT_TCP entries (VPCSUM_NAT_TCP_REWRITES batches only; 48-B
+// entries): a pass of its own after the address / port / TTL rewrite on the same stream, so k_natq /
+// k_natw / k_nat stay as they are.  One lane per packet; most packets carry no TCP op and leave on
+// the entry's mask dword (4 of its 48 bytes read).  The rest work with byte accesses on the frame
+// (tcp_rewrite.h): L3 has any alignment, an MSS option after a NOP sits at an odd address, and a
+// TCP header behind IPv4 options / IPv6 extension headers ends past the wide window.  res[p] is
+// read and written as a byte: its dword is shared with three other lanes.
+//   PH 0 (RFC 1624)  res = status of the first pass: packets it refused are skipped; rewrite, the
+//                    stored TCP sum updated by eqn. 3 over the changed bytes; S_MSS_ABSENT.
+//   PH 1 (strict)    res = the first pass's dirty flags (kFlagRejected: skipped); rewrite, F_L4
+//                    added when Java's setters marked the sum dirty -- the recompute pass follows.
+//   PH 2 (strict)    res = the status after the recompute: S_MSS_ABSENT from the bytes as they
+//                    are now, the way k_nat_ttl_status derives S_TTL_EXPIRED.
+template <int PH>
+__global__ __launch_bounds__(256) void k_nat_tcp(uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                const uint4* __restrict__ desc, const uint32_t* __restrict__ rw,
+                                                uint32_t n, uint8_t* __restrict__ res) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        const uint32_t* e = rw + 12 * (size_t)p;   // vpcsum_nat_t: 12 dwords, the mask in dword 9
+        const uint32_t y = e[9];
+        if (!(y & VPCSUM_NAT_TCP)) continue;
+        const TcpRw r = tcp_rw_decode(y, e[10], e[11]);
+        if (!r.ops) continue;
+        const uint32_t was = res[p];
+        if (was & (PH == 1 ? (uint32_t)kFlagRejected : (uint32_t)VPCSUM_S_BAD_DESC)) continue;
+        const uint4 dv = desc[p];
+        const uint64_t off = (uint64_t)dv.x | ((uint64_t)dv.y << 32);
+        const int len = dv.z & 0xffff, l4o = dv.z >> 16;
+        const int ver = dv.w & 0xff, proto = (dv.w >> 8) & 0xff;
+        // the first pass's bounds rule once more: the status byte alone never lets a frame be written
+        if (!nat_desc_ok(off, len, l4o, ver, arena_len, 1) || !tcp_rw_applies(proto, len, l4o)) continue;
+        uint8_t* t = arena + off + l4o;
+        const uint32_t seg = (uint32_t)(len - l4o);
+        if (PH == 2) {
+            if (tcp_mss_absent(t, seg, r)) res[p] = (uint8_t)(was | VPCSUM_S_MSS_ABSENT);
+            continue;
+        }
+        const TcpRes o = tcp_rewrite(t, seg, r);
+        if (PH == 0) {
+            if (o.dirty) tcp_sum_update(t, o.diff);
+            if (o.absent) res[p] = (uint8_t)(was | VPCSUM_S_MSS_ABSENT);
+        } else if (o.dirty && !(was & VPCSUM_F_L4)) {
+            res[p] = (uint8_t)(was | VPCSUM_F_L4);
+        }
+    }
+}
+
+hipError_t launch_nat_tcp(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, uint32_t n,
+                          uint8_t* res, int phase, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    uint32_t g = (n + 255) / 256;
+    const uint32_t cap = (uint32_t)num_cus(dev) * 8;
+    if (g > cap) g = cap;
+    const uint4* d = (const uint4*)desc;
+    const uint32_t* e = (const uint32_t*)rw;
+    if (phase == 0)
+        hipLaunchKernelGGL(k_nat_tcp<0>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, e, n, res);
+    else if (phase == 1)
+        hipLaunchKernelGGL(k_nat_tcp<1>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, e, n, res);
+    else
+        hipLaunchKernelGGL(k_nat_tcp<2>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, e, n, res);
     return hipGetLastError();
 }
 

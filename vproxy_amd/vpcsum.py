@@ -22,6 +22,11 @@ S_TTL_EXPIRED = 0x20
 MODE_COMPUTE, MODE_VERIFY, MODE_WRITE = 0x00, 0x01, 0x10
 NAT_SRC, NAT_DST, NAT_SPORT, NAT_DPORT, NAT_DEC_TTL, NAT_SET_TTL = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 NAT_RFC1624, NAT_STRICT_JAVA = 0x00, 0x01
+# TCP-header rewrites of a NAT'd packet (include/vpcsum.h): NAT_TCP in a NAT_DTYPE entry's mask says
+# its rsv[0..7] hold them (nat_tcp_fill), honoured only in a batch run with the NAT_TCP_REWRITES mode
+# bit; S_MSS_ABSENT: a clamp on a SYN without an MSS option (the caller adds it on the host)
+NAT_TCP, NAT_TCP_REWRITES, S_MSS_ABSENT = 0x40, 0x02, 0x08
+TCP_SEQ_ADD, TCP_SET_FLAGS, TCP_CLAMP_MSS = 0x01, 0x02, 0x04
 PRE_FMT_PRE4, PRE_FMT_PRE = 0, 1   # pre-image entries: NAT4_DTYPE (16 B, IPv4) / NAT_DTYPE (48 B)
 PRE_HSUM = 0x80   # pre-image entry mask: the entry's first 8 bytes hold an HSUM_DTYPE record
 ABI_VERSION = 4   # include/vpcsum.h VPCSUM_ABI_VERSION: the library this binding was written against
@@ -307,6 +312,19 @@ def nat(arena, desc, rw, n: int, status=None, nat_mode: int = NAT_RFC1624, strea
     """NAT / TTL rewrite with 48-B vpcsum_nat_t entries (IPv4 and IPv6): `rw` a uint8 tensor of n x 48."""
     _check(lib().vpcsum_nat_async(_ptr(arena), arena.numel(), _ptr(desc), _ptr(rw), n, _ptr(status), nat_mode,
                                   _stream(stream)), "vpcsum_nat_async")
+
+
+def nat_tcp_fill(entry, seq_add: int | None = None, flags: int | None = None, max_mss: int | None = None):
+    """Fill the TCP part of one NAT_DTYPE entry (`entry`: rw[i]): seq_add the sequence addend (any
+    sign, taken mod 2^32: seq - N is -N), flags the new TCP flags (low 6 bits), max_mss the MSS
+    clamp of a SYN; None leaves that rewrite out.  Sets NAT_TCP in the mask; the batch needs the
+    NAT_TCP_REWRITES mode bit."""
+    ops = (TCP_SEQ_ADD if seq_add is not None else 0) | (TCP_SET_FLAGS if flags is not None else 0) | \
+          (TCP_CLAMP_MSS if max_mss is not None else 0)
+    rsv = bytes([ops, (flags or 0) & 0x3F]) + ((max_mss or 0) & 0xFFFF).to_bytes(2, "big") + \
+        ((seq_add or 0) & 0xFFFFFFFF).to_bytes(4, "big") + b"\x00\x00"
+    entry["rsv"] = np.frombuffer(rsv, np.uint8)
+    entry["mask"] = int(entry["mask"]) | NAT_TCP
 
 
 def pre(arena, desc, pre_img, n: int, out=None, status=None, mode: int = MODE_WRITE, pre_fmt: int = PRE_FMT_PRE4,
