@@ -104,6 +104,36 @@ def test_batch_plan_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "batch_plan ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+@pytest.fixture(scope="module")
+def launch_modes_run(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("launch_modes") / "launch_modes_test"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "vproxy_amd", "csrc"),
+                           os.path.join(REPO, "tests", "cpp", "launch_modes_test.cpp"), "-o", str(exe)])
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+
+
+def test_launch_modes_under_sanitizers(launch_modes_run):
+    """The mode-word decoders (vproxy_amd/csrc/launch_modes.h: accept masks, csum_tune, nat_build,
+    nat_probe_build, pre_build) equal a transcription of the launch ladders they replaced on every
+    combination of the bits they read, and reach exactly the builds the launchers instantiate
+    (tests/cpp/launch_modes_test.cpp, stand-alone under ASan / UBSan)."""
+    r = launch_modes_run
+    assert r.returncode == 0 and "launch_modes ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
+def test_launch_modes_builds_are_the_kernels_built(launch_modes_run):
+    """As many NAT / pre-image builds are reachable through the mode words as the code object holds
+    k_nat / k_natw / k_natq / k_pre kernels (probes included): a dispatcher that instantiates more
+    than the decoders can ask for, or a decoder asking for a kernel that is not built, fails here."""
+    from test_kernel_resources import kernels
+    ks = kernels("nat.hip.o")
+    m = re.search(r"nat builds (\d+) pre builds (\d+)", launch_modes_run.stdout)
+    assert m, launch_modes_run.stdout
+    assert int(m.group(1)) == len([k for k in ks if re.search(r"k_nat[wq]?ILi", k)])
+    assert int(m.group(2)) == len([k for k in ks if re.search(r"k_preILi", k)])
+
+
 def test_survey_entry_points_refuse_before_init(libpath):
     """SURVEY.md §8(b)'s names (vpcsum_init / vpcsum_batch_submit / vpcsum_batch_wait /
     vpcsum_nat_submit) work over one process-wide group; before vpcsum_init every one of them

@@ -324,27 +324,16 @@ int vpcsum_set_device(int device) {
     } VPC_CATCH("vpcsum_set_device")
 }
 
-// kernel variant id: bits 8..12 low, bits 24..26 high (0..255; 0 = default)
-static int team_from_mode(uint32_t mode) { return (int)(((mode >> 8) & 0x1f) | (((mode >> 24) & 0x7) << 5)); }
-
 int vpcsum_compute_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, uint32_t n,
                          uint32_t* d_out, uint8_t* d_status, uint32_t mode, void* stream) {
     try {
         if (n == 0) return 0;
         if (!d_arena || !d_desc) return fail("vpcsum_compute_async: NULL arena or descriptors");
-        // tuning hints (not part of the stable ABI): bits 8..12 + 24..26 kernel variant, bit 13
-        // plain (temporal) loads, bit 14 no sampled low-concurrency grid, bits 16..23 workgroups
-        // per CU.
-        if (mode & ~(0x07ff7fffu | VPCSUM_MODE_VERIFY | VPCSUM_MODE_WRITE)) return fail("vpcsum_compute_async: bad mode 0x%x", mode);
+        // beyond VERIFY and WRITE: tuning hints, not part of the stable ABI (launch_modes.h)
+        if (mode & ~kCsumModeAccept) return fail("vpcsum_compute_async: bad mode 0x%x", mode);
         uint8_t* w = (mode & VPCSUM_MODE_WRITE) ? const_cast<uint8_t*>(d_arena) : nullptr;
-        int grid = 0;
-        if ((mode >> 16) & 0xff) {
-            int dev = 0;
-            VPC_CHECK(hipGetDevice(&dev), "hipGetDevice");
-            grid = num_cus(dev) * (int)((mode >> 16) & 0xff);
-        }
-        VPC_CHECK(launch_csum(d_arena, arena_len, d_desc, n, d_out, d_status, nullptr, mode, w, team_from_mode(mode), grid,
-                              (hipStream_t)stream),
+        VPC_CHECK(launch_csum(d_arena, arena_len, d_desc, n, d_out, d_status, nullptr, (mode & VPCSUM_MODE_VERIFY) != 0, w,
+                              csum_tune(mode), (hipStream_t)stream),
                   "vpcsum_compute_async launch");
         return 0;
     } VPC_CATCH("vpcsum_compute_async")
@@ -447,13 +436,13 @@ static int nat_run(uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_
     // VPCSUM_NAT_TCP_REWRITES (48-B entries, a status buffer: the callers' checks): the TCP-header
     // rewrites of VPCSUM_NAT_TCP entries, a pass of their own after the rewrite
     const bool tcp = (nat_mode & VPCSUM_NAT_TCP_REWRITES) != 0;
+    const NatBuild build = nat_build(nat_mode, fmt);
     if (nat_mode & VPCSUM_NAT_STRICT_JAVA) {
         // pass 1: rewrite fields, record which sums went dirty (Java's checksumSkipped())
-        VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, fmt, n, nullptr, d_status, nat_mode, s), "nat launch");
+        VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, n, nullptr, d_status, build, s), "nat launch");
         if (tcp) VPC_CHECK(launch_nat_tcp(d_arena, arena_len, d_desc, d_rw, n, d_status, 1, s), "nat tcp launch");
         // pass 2: full recompute of the dirty sums, written in place (getRawPacket(0))
-        VPC_CHECK(launch_csum(d_arena, arena_len, d_desc, n, nullptr, d_status, d_status, VPCSUM_MODE_WRITE, d_arena,
-                              0, 0, s),
+        VPC_CHECK(launch_csum(d_arena, arena_len, d_desc, n, nullptr, d_status, d_status, false, d_arena, CsumTune{}, s),
                   "nat recompute launch");
         // pass 3: the TTL-expired packets (refused, untouched) get S_TTL_EXPIRED next to S_BAD_DESC
         VPC_CHECK(launch_nat_ttl_status(d_arena, arena_len, d_desc, d_rw, fmt, n, d_status, s), "nat ttl status launch");
@@ -461,7 +450,7 @@ static int nat_run(uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_
         if (tcp) VPC_CHECK(launch_nat_tcp(d_arena, arena_len, d_desc, d_rw, n, d_status, 2, s), "nat tcp status launch");
         return 0;
     }
-    VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, fmt, n, d_status, nullptr, nat_mode, s), "nat launch");
+    VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, n, d_status, nullptr, build, s), "nat launch");
     if (tcp) VPC_CHECK(launch_nat_tcp(d_arena, arena_len, d_desc, d_rw, n, d_status, 0, s), "nat tcp launch");
     return 0;
 }
@@ -470,11 +459,8 @@ static int nat_async(const char* what, uint8_t* d_arena, uint64_t arena_len, con
                      const void* d_rw, int fmt, uint32_t n, uint8_t* d_status, uint32_t nat_mode, void* stream) {
     if (n == 0) return 0;
     if (!d_arena || !d_desc || !d_rw) return fail("%s: NULL arena, descriptors or rewrite table", what);
-    // tuning hints (not part of the stable ABI; nat.hip, above nat_chunks_sel): bit 8 byte-access
-    // kernel, bits 12..14 packets per lane of the wide kernel (the quad kernel clamps 4 to 2), bits
-    // 16..17 window chunks, bits 18..22 workgroups per CU, bit 23 the lane layout of the wide kernel
-    // instead of quads, bits 24..25 the quad kernel's forced occupancy (6 / 8 waves: may spill)
-    if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | VPCSUM_NAT_TCP_REWRITES | 0x100u | 0x7000u | 0x3ff0000u))
+    // beyond the two mode bits: tuning hints, not part of the stable ABI (launch_modes.h)
+    if (nat_mode & ~kNatModeAccept)
         return fail("%s: bad nat_mode 0x%x", what, nat_mode);
     if ((nat_mode & VPCSUM_NAT_TCP_REWRITES) && fmt != 1)
         return fail("%s: VPCSUM_NAT_TCP_REWRITES takes 48-byte vpcsum_nat_t entries only (vpcsum_nat_async)", what);
@@ -484,12 +470,22 @@ static int nat_async(const char* what, uint8_t* d_arena, uint64_t arena_len, con
     return nat_run(d_arena, arena_len, d_desc, d_rw, fmt, n, d_status, nat_mode, (hipStream_t)stream);
 }
 
+// tooling: the pattern probes take the tuning fields of a nat_mode word from the environment
+static uint32_t nat_probe_tune() {
+    static const uint32_t tune = [] {
+        const char* e = getenv("VPCSUM_NAT_PROBE_TUNE");
+        return e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
+    }();
+    return tune;
+}
+
 int vpcsum_nat4_pattern_probe_async(uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc,
                                     const vpcsum_nat4_t* d_rw, uint32_t n, void* stream) {
     try {
         if (n == 0) return 0;
         if (!d_arena || !d_desc || !d_rw) return fail("vpcsum_nat4_pattern_probe_async: NULL argument");
-        VPC_CHECK(launch_nat_probe(d_arena, arena_len, d_desc, d_rw, 0, n, (hipStream_t)stream),
+        VPC_CHECK(launch_nat(d_arena, arena_len, d_desc, d_rw, n, nullptr, nullptr, nat_probe_build(nat_probe_tune(), 0),
+                             (hipStream_t)stream),
                   "vpcsum_nat4_pattern_probe_async launch");
         return 0;
     } VPC_CATCH("vpcsum_nat4_pattern_probe_async")
@@ -515,7 +511,8 @@ int vpcsum_nat4r_pattern_probe_async(uint8_t* d_arena, uint64_t arena_len, const
     try {
         if (n == 0) return 0;
         if (!d_arena || !d_rec) return fail("vpcsum_nat4r_pattern_probe_async: NULL argument");
-        VPC_CHECK(launch_nat_probe(d_arena, arena_len, (const vpcsum_desc_t*)d_rec, d_rec, 2, n, (hipStream_t)stream),
+        VPC_CHECK(launch_nat(d_arena, arena_len, (const vpcsum_desc_t*)d_rec, d_rec, n, nullptr, nullptr,
+                             nat_probe_build(nat_probe_tune(), 2), (hipStream_t)stream),
                   "vpcsum_nat4r_pattern_probe_async launch");
         return 0;
     } VPC_CATCH("vpcsum_nat4r_pattern_probe_async")
@@ -534,13 +531,10 @@ int vpcsum_pre_async(uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* 
         if (n == 0) return 0;
         if (!d_arena || !d_desc || !d_pre) return fail("vpcsum_pre_async: NULL arena, descriptors or pre-images");
         if (pre_fmt > VPCSUM_PRE_FMT_PRE) return fail("vpcsum_pre_async: bad pre_fmt %u", pre_fmt);
-        // tuning hints (not part of the stable ABI; nat.hip launch_pre): bit 8 byte accesses on the
-        // frames, bits 12..13 packets per lane (2: two; default one), bits 16..17 window chunks (2:
-        // four, 16-B entries only), bits 18..22 workgroups per CU, bit 23 the memory-pattern probe
-        // (16-B entries: the same loads and stores, the stored sums written back unchanged), bit 24
-        // non-temporal field stores
-        if (mode & ~(VPCSUM_MODE_WRITE | 0x100u | 0x3000u | 0x1ff0000u)) return fail("vpcsum_pre_async: bad mode 0x%x", mode);
-        VPC_CHECK(launch_pre(d_arena, arena_len, d_desc, d_pre, (int)pre_fmt, n, d_out, d_status, mode, (hipStream_t)stream),
+        // beyond WRITE: tuning hints, not part of the stable ABI (launch_modes.h)
+        if (mode & ~kPreModeAccept) return fail("vpcsum_pre_async: bad mode 0x%x", mode);
+        VPC_CHECK(launch_pre(d_arena, arena_len, d_desc, d_pre, n, d_out, d_status, pre_build(mode, (int)pre_fmt),
+                             (hipStream_t)stream),
                   "vpcsum_pre_async launch");
         return 0;
     } VPC_CATCH("vpcsum_pre_async")
@@ -1054,7 +1048,11 @@ static int slot_rw_alloc(vpcsum_ctx* c, Slot& s, const char* what) {
 // Zero-copy batches of up to kZeroCopyWaveTeams packets run one wave per packet (variant 12, 64
 // lanes x 4 predicated loads): the batch is a few PCIe round trips deep instead of K2's per-unit
 // iterations, and no chunk is read twice over PCIe.
-static int zero_copy_variant(uint32_t n) { return n <= kZeroCopyWaveTeams ? 12 : 0; }
+static CsumTune zero_copy_tune(uint32_t n) {
+    CsumTune t;
+    t.variant = n <= kZeroCopyWaveTeams ? 12 : 0;
+    return t;
+}
 
 // The service runs one batch at a time: the previous one done, its results handed over, before its
 // buffers are refilled.  (An idle grid stays resident beside launched batches: the stop round 5 had
@@ -1190,8 +1188,8 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
             memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
             // no out words asked for (an ingress verify: the status bytes are the result): none written
             VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
-                                  mode & VPCSUM_MODE_VERIFY, (mode & VPCSUM_MODE_WRITE) ? base : nullptr,
-                                  zero_copy_variant(n), 0, s.stream),
+                                  (mode & VPCSUM_MODE_VERIFY) != 0, (mode & VPCSUM_MODE_WRITE) ? base : nullptr,
+                                  zero_copy_tune(n), s.stream),
                       "checksum launch (zero-copy)");
             b.zero_copy = true;
         } else {
@@ -1225,7 +1223,7 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
             // the out words travel when the caller asked for them or MODE_WRITE places them in the frames
             const bool want_out = h_out || (mode & VPCSUM_MODE_WRITE);
             VPC_CHECK(launch_csum(s.d_arena, dev_len, s.d_desc, n, want_out ? s.d_out : nullptr, s.d_status, nullptr,
-                                  mode & VPCSUM_MODE_VERIFY, nullptr, 0, 0, s.stream),
+                                  (mode & VPCSUM_MODE_VERIFY) != 0, nullptr, CsumTune{}, s.stream),
                       "checksum launch");
             if (want_out)
                 VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
@@ -1278,10 +1276,11 @@ int vpcsum_ctx_submit_pre(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
             // registered arena (umem): in place; an F_PRE packet's header is all that crosses PCIe
             memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
             if (full)
-                VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, s.h_out.dev, s.h_status.dev, nullptr, VPCSUM_MODE_COMPUTE,
-                                      wr ? base : nullptr, zero_copy_variant(n), 0, s.stream),
+                VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, s.h_out.dev, s.h_status.dev, nullptr, false,
+                                      wr ? base : nullptr, zero_copy_tune(n), s.stream),
                           "checksum launch (zero-copy)");
-            VPC_CHECK(launch_pre(base, arena_len, s.h_desc.dev, s.h_rw.dev, (int)pre_fmt, n, s.h_out.dev, s.h_status.dev, wr, s.stream),
+            VPC_CHECK(launch_pre(base, arena_len, s.h_desc.dev, s.h_rw.dev, n, s.h_out.dev, s.h_status.dev,
+                                 pre_build(wr, (int)pre_fmt), s.stream),
                       "pre-image launch (zero-copy)");
             b.zero_copy = true;
         } else {
@@ -1311,11 +1310,12 @@ int vpcsum_ctx_submit_pre(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
             VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw.p, (size_t)n * esz, hipMemcpyHostToDevice, s.stream), "H2D pre-images");
             if (pos) VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, pos, hipMemcpyHostToDevice, s.stream), "H2D frames");
             if (full)
-                VPC_CHECK(launch_csum(s.d_arena, pos, s.d_desc, n, s.d_out, s.d_status, nullptr, VPCSUM_MODE_COMPUTE, nullptr,
-                                      0, 0, s.stream),
+                VPC_CHECK(launch_csum(s.d_arena, pos, s.d_desc, n, s.d_out, s.d_status, nullptr, false, nullptr,
+                                      CsumTune{}, s.stream),
                           "checksum launch");
             // the sums go back through out: slot_finish writes them into the caller's frames
-            VPC_CHECK(launch_pre(s.d_arena, pos, s.d_desc, s.d_rw, (int)pre_fmt, n, s.d_out, s.d_status, 0, s.stream),
+            VPC_CHECK(launch_pre(s.d_arena, pos, s.d_desc, s.d_rw, n, s.d_out, s.d_status, pre_build(0, (int)pre_fmt),
+                                 s.stream),
                       "pre-image launch");
             VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
             VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
@@ -1398,7 +1398,7 @@ static int ctx_verify_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t a
                       "parse launch");
             // h_out NULL: the status bytes alone (the out words are 4 of the 5 result bytes a packet writes)
             VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
-                                  VPCSUM_MODE_VERIFY, nullptr, zero_copy_variant(n), 0, s.stream),
+                                  true, nullptr, zero_copy_tune(n), s.stream),
                       "verify launch");
         }
         return slot_commit(s, b, ticket);
@@ -1443,8 +1443,8 @@ int vpcsum_ctx_egress_frames(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_l
                 VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, 0, s.d_desc, nullptr, nullptr,
                                              s.stream, s.h_status.dev),
                           "parse launch");
-                VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, s.h_out.dev, s.h_status.dev, nullptr, VPCSUM_MODE_COMPUTE,
-                                      base, zero_copy_variant(n), 0, s.stream),
+                VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, s.h_out.dev, s.h_status.dev, nullptr, false,
+                                      base, zero_copy_tune(n), s.stream),
                           "checksum launch");
             }
             return slot_commit(s, b, ticket);
@@ -1487,7 +1487,7 @@ int vpcsum_ctx_nat_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
         if (!c || !ticket) return fail("vpcsum_ctx_nat_submit: NULL context or ticket");
         if (n > c->max_pkts) return fail("vpcsum_ctx_nat_submit: %u packets > capacity %u", n, c->max_pkts);
         if (n && (!h_arena || !h_desc || !h_rw)) return fail("vpcsum_ctx_nat_submit: NULL arena, descriptors or rewrites");
-        if (nat_mode & ~(VPCSUM_NAT_STRICT_JAVA | VPCSUM_NAT_TCP_REWRITES | 0x100u))
+        if (nat_mode & ~kNatCtxModeAccept)
             return fail("vpcsum_ctx_nat_submit: bad nat_mode 0x%x", nat_mode);
         // without the status bytes the caller would never see S_MSS_ABSENT, its part of the clamp
         if ((nat_mode & VPCSUM_NAT_TCP_REWRITES) && !h_status)
@@ -1596,7 +1596,7 @@ int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint
                                        hipMemcpyHostToDevice, s.stream),
                       "pipeline H2D frames");
             VPC_CHECK_DRAIN(launch_csum(s.d_arena - (uint64_t)i0 * stride, (uint64_t)(i0 + m) * stride, s.d_desc, m, s.d_out,
-                                  nullptr, nullptr, mode & VPCSUM_MODE_VERIFY, w, 0, 0, s.stream),
+                                  nullptr, nullptr, (mode & VPCSUM_MODE_VERIFY) != 0, w, CsumTune{}, s.stream),
                       "pipeline launch");
             VPC_CHECK_DRAIN(hipMemcpyAsync(h_out + i0, s.d_out, (size_t)m * 4, hipMemcpyDeviceToHost, s.stream), "pipeline D2H");
         }

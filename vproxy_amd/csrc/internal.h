@@ -3,15 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "launch_modes.h"
 #include "vpcsum.h"
 
 namespace vpcsum {
 
-// Lanes per packet ("team") for the checksum kernel.  0 = auto.
-// mode bits 8..11 carry an explicit log2(team) (tuning / tests); see api.cpp.
+// The checksum of a batch.  `tune` picks the kernel variant, the loads' cache policy and the grid
+// (launch_modes.h csum_tune; default-constructed: the default kernel on its own grid).  arena_w:
+// where the sums are written in place (VPCSUM_MODE_WRITE), or NULL.
 hipError_t launch_csum(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, uint32_t n,
-                       uint32_t* out, uint8_t* status, const uint8_t* flags_override, uint32_t mode,
-                       uint8_t* arena_w, int team_log2, int grid_override, hipStream_t stream);
+                       uint32_t* out, uint8_t* status, const uint8_t* flags_override, bool verify,
+                       uint8_t* arena_w, const CsumTune& tune, hipStream_t stream);
 
 // Low-latency service (k_csum_service): a small persistent grid that polls this host-pinned,
 // device-mapped, uncached mailbox instead of being launched per batch.  The host writes the
@@ -69,17 +71,17 @@ hipError_t launch_service(SvcMailbox* d_mb, uint32_t* d_ctr, uint32_t seen, uint
 // (100 MHz) -- no memory traffic: the control for "a resident kernel on another queue" A/Bs.
 hipError_t launch_spin_probe(uint32_t wgs, uint32_t threads, uint64_t ticks, hipStream_t stream);
 
-// NAT / TTL rewrites (nat.hip).  fmt 0: rw is vpcsum_nat4_t[n], fmt 1: vpcsum_nat_t[n].  With
-// VPCSUM_NAT_STRICT_JAVA the kernel only rewrites and stores Java's dirty flags in flags_out.
-hipError_t launch_nat(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, int fmt,
-                      uint32_t n, uint8_t* status, uint8_t* flags_out, uint32_t nat_mode, hipStream_t stream);
-// NAT's memory operations without the rewrite (tooling: the C5 pattern ceiling)
-hipError_t launch_nat_probe(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, int fmt,
-                            uint32_t n, hipStream_t stream);
-// pre-image egress sums (K6, VPCSUM_F_PRE descriptors only); fmt 0: vpcsum_pre4_t, 1: vpcsum_pre_t;
-// mode: VPCSUM_MODE_WRITE plus the tuning bits of vpcsum_pre_async
-hipError_t launch_pre(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* pre, int fmt, uint32_t n,
-                      uint32_t* out, uint8_t* status, uint32_t mode, hipStream_t stream);
+// NAT / TTL rewrites (nat.hip), the kernel `build` names (launch_modes.h nat_build).  fmt 0: rw is
+// vpcsum_nat4_t[n], fmt 1: vpcsum_nat_t[n], fmt 2: desc and rw are the same vpcsum_nat4_rec_t[n].
+// With VPCSUM_NAT_STRICT_JAVA the kernel only rewrites and stores Java's dirty flags in flags_out.
+// A probe build (nat_probe_build) runs NAT's memory operations without the rewrite (tooling: the C5
+// pattern ceiling) and takes neither status nor flags_out.
+hipError_t launch_nat(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, uint32_t n,
+                      uint8_t* status, uint8_t* flags_out, const NatBuild& build, hipStream_t stream);
+// pre-image egress sums (K6, VPCSUM_F_PRE descriptors only); fmt 0: vpcsum_pre4_t, 1: vpcsum_pre_t
+// (launch_modes.h pre_build)
+hipError_t launch_pre(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* pre, uint32_t n,
+                      uint32_t* out, uint8_t* status, const PreBuild& build, hipStream_t stream);
 // strict mode, after the recompute: S_TTL_EXPIRED on the packets refused for their TTL
 hipError_t launch_nat_ttl_status(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw,
                                  int fmt, uint32_t n, uint8_t* status, hipStream_t stream);

@@ -508,15 +508,13 @@ static hipError_t launch_team(const uint8_t* arena, uint64_t arena_len, const vp
     uint32_t g = grid > 0 ? (uint32_t)grid : need;
     if (g > need) g = need;
     if (g == 0) g = 1;
-#define VPC_LAUNCH(V, N)                                                                                         \
-    hipLaunchKernelGGL((k_csum<TEAM, U, V, N, PRED>), dim3(g), dim3(256), 0, stream, arena, arena_len,                   \
-                       (const uint4*)desc, n, out, status, flags_override, arena_w)
-    if (verify) {
-        if (nt) VPC_LAUNCH(true, true); else VPC_LAUNCH(true, false);
-    } else {
-        if (nt) VPC_LAUNCH(false, true); else VPC_LAUNCH(false, false);
-    }
-#undef VPC_LAUNCH
+    dispatch(
+        [&](auto V, auto N) {
+            hipLaunchKernelGGL((k_csum<TEAM, U, V, N, PRED>), dim3(g), dim3(256), 0, stream, arena, arena_len,
+                               (const uint4*)desc, n, out, status, flags_override, arena_w);
+            return true;
+        },
+        verify, AmongBool{}, nt, AmongBool{});
     return hipGetLastError();
 }
 
@@ -1346,22 +1344,45 @@ __device__ __forceinline__ void k2_run(const uint8_t* __restrict__ arena, uint64
     if (DS && stage) es_flush();
 }
 
+// One K2 build: k2_run's template arguments but VERIFY and NT, which launch_d picks per batch.
+template <int TEAM, int U, int TS = 0, int US = 1, int WPE = 1, int IL = 0, int ROT = 0, bool SF = false, bool WT = false,
+          bool DS = false, bool WIN = false, bool WGS = false>
+struct K2Build {
+    static constexpr int team = TEAM, u = U, ts = TS, us = US, wpe = WPE, il = IL, rot = ROT;
+    static constexpr bool sf = SF, wt = WT, ds = DS, win = WIN, wgs = WGS;
+};
+// The default shape (teams of 8 x 6 chunks, small tier 2 x 2, rotated units) and what varies on it:
+// window units (SF), the WT A/B, staged result stores (DS), a pass per 2-GiB window for arenas past
+// 4 GiB (WIN), workgroup-sorted units (WGS).
+template <bool SF, bool WT, bool DS, bool WIN, bool WGS>
+using K2Default = K2Build<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, SF, WT, DS, WIN, WGS>;
+//                                        SF     WT     DS     WIN    WGS
+using K2Dense          = K2Default<true,  false, false, false, false>;   // dense small frames: no staging
+using K2Staged         = K2Default<true,  false, true,  false, true>;    // everything else (id 84)
+using K2DenseWin       = K2Default<true,  false, false, true,  false>;   // their builds for arenas past 4 GiB
+using K2StagedWin      = K2Default<true,  false, true,  true,  false>;
+using K2NoWindowUnits  = K2Default<false, false, false, false, false>;   // A/B, id 72
+using K2NoStaging      = K2Dense;                                        // A/B, id 76: K2Dense on every batch
+using K2StagedUnsorted = K2Default<true,  false, true,  false, false>;   // A/B, id 79 (round 3's default)
+using K2WtAB           = K2Default<true,  true,  false, false, false>;   // A/B, id 74
+
 // Occupancy of a K2 build: WPE > 1 forces that many waves per SIMD (tuning variants).  The default
 // shape's verify and staging builds are held to 6 (80 VGPRs), the unstaged compute build's natural
 // count: left alone, the compiler gave them 95 and 92 (5 waves) -- the verify build for its stored
 // fields, the staging build because its 26 KB of LDS let it budget for fewer resident waves
 // (DESIGN.md §5 items 25, 28).  tests/test_kernel_resources.py holds all of them to 80, no scratch.
-template <int TEAM, int U, int TS, int US, bool VERIFY, int WPE, int IL, int ROT, bool SF, bool WT, bool DS, bool WIN = false, bool WGS = false>
+// In the builds' names: every default-shape build but K2Dense's compute build; not the A/B builds
+// K2NoWindowUnits and K2WtAB.
+template <class B, bool VERIFY>
 constexpr int k2_waves_per_eu() {
-    return WPE > 1 ? WPE
-                   : (TEAM == kDefaultTeam && U == kDefaultUnroll && TS == kSmallTeam && US == kSmallUnroll &&
-                      IL == 0 && ROT == kDefaultRot && SF && !WT && (VERIFY || DS || WIN || WGS))
-                         ? 6
-                         : 1;
+    constexpr bool default_shape = std::is_same_v<B, K2Dense> || std::is_same_v<B, K2Staged> ||
+                                   std::is_same_v<B, K2StagedUnsorted> || std::is_same_v<B, K2DenseWin> ||
+                                   std::is_same_v<B, K2StagedWin>;
+    return B::wpe > 1 ? B::wpe : (default_shape && (VERIFY || !std::is_same_v<B, K2Dense>)) ? 6 : 1;
 }
 
 template <int TEAM, int U, int TS, int US, bool VERIFY, bool NT, int WPE = 1, int IL = 0, int ROT = 0, bool SF = false, bool WT = false, bool DS = false, bool WIN = false, bool WGS = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(k2_waves_per_eu<TEAM, U, TS, US, VERIFY, WPE, IL, ROT, SF, WT, DS, WIN, WGS>()))) void k_csum_d(const uint8_t* __restrict__ arena, uint64_t arena_len,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(k2_waves_per_eu<K2Build<TEAM, U, TS, US, WPE, IL, ROT, SF, WT, DS, WIN, WGS>, VERIFY>()))) void k_csum_d(const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                 const uint4* __restrict__ desc, uint32_t n,
                                                 uint32_t* __restrict__ out, uint8_t* __restrict__ status,
                                                 const uint8_t* __restrict__ flags_override,
@@ -1635,64 +1656,66 @@ static uint32_t default_low_grid() {
     return (uint32_t)num_cus(dev) * 2u;
 }
 
-template <int TEAM, int U, int TS = 0, int US = 1, int WPE = 1, int IL = 0, int ROT = 0, bool SF = false, bool WT = false, bool DS = false, bool WIN = false, bool WGS = false>
+template <class B>
 static hipError_t launch_d(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, uint32_t n,
                            uint32_t* out, uint8_t* status, const uint8_t* flags_override, bool verify, bool nt,
                            uint8_t* arena_w, int grid, bool adapt, hipStream_t stream) {
-    if ((!WIN && arena_len > kMaxBufArena) || ((uintptr_t)arena & 15))
-        return launch_team<TEAM, U>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w,
-                                    grid > 0 ? grid : default_grid(), stream);
+    if ((!B::win && arena_len > kMaxBufArena) || ((uintptr_t)arena & 15))
+        return launch_team<B::team, B::u>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w,
+                                          grid > 0 ? grid : default_grid(), stream);
     uint32_t need = (n + 255) / 256;   // 4 waves x 64 packets per workgroup
     uint32_t g = grid > 0 ? (uint32_t)grid : default_grid();
     // sampled low-concurrency grid: default grid only, not with IL (its units are per workgroup),
     // and only when the arena is large enough to hold n packets of >= 1 KiB without overlap
     // (otherwise the sample cannot succeed and its load latency would be pure cost)
     const uint32_t low_grid =
-        (grid > 0 || IL == 1 || !adapt || arena_len < (uint64_t)n * 1024u) ? 0u : default_low_grid();
+        (grid > 0 || B::il == 1 || !adapt || arena_len < (uint64_t)n * 1024u) ? 0u : default_low_grid();
     // Dense small frames (at most 128 arena bytes per packet): one resident round of workgroups
     // beats the grid-stride default (C1 window units at 6 per CU: 4.91 vs 4.63 TB/s at 5 and
     // 4.65 at 12); the arena size alone tells, no sample needed.
-    const bool dense = grid <= 0 && adapt && IL != 1 && arena_len <= (uint64_t)n * 128u;
+    const bool dense = grid <= 0 && adapt && B::il != 1 && arena_len <= (uint64_t)n * 128u;
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint32_t cus = (uint32_t)num_cus(dev);
-#define VPC_LAUNCH(V, N)                                                                                         \
-    do {                                                                                                         \
-        auto kern = k_csum_d<TEAM, U, TS, US, V, N, WPE, IL, ROT, SF, WT, DS, WIN, WGS>;                             \
-        uint32_t gg = g;                                                                                         \
-        if (dense) {                                                                                             \
-            static const uint32_t res = resident_wgs((const void*)kern);                                         \
-            gg = min(gg, res * cus);                                                                             \
-        }                                                                                                        \
-        if (gg > need) gg = need;                                                                                \
-        if (gg == 0) gg = 1;                                                                                     \
-        hipLaunchKernelGGL(kern, dim3(gg), dim3(256), 0, stream, arena, arena_len, (const uint4*)desc, n, out,   \
-                           status, flags_override, arena_w, low_grid);                                            \
-    } while (0)
-    if (verify) {
-        if (nt) VPC_LAUNCH(true, true); else VPC_LAUNCH(true, false);
-    } else {
-        if (nt) VPC_LAUNCH(false, true); else VPC_LAUNCH(false, false);
-    }
-#undef VPC_LAUNCH
+    dispatch(
+        [&](auto V, auto N) {
+            auto kern = k_csum_d<B::team, B::u, B::ts, B::us, V, N, B::wpe, B::il, B::rot, B::sf, B::wt, B::ds, B::win, B::wgs>;
+            uint32_t gg = g;
+            if (dense) {
+                static const uint32_t res = resident_wgs((const void*)kern);   // once per kernel
+                gg = min(gg, res * cus);
+            }
+            if (gg > need) gg = need;
+            if (gg == 0) gg = 1;
+            hipLaunchKernelGGL(kern, dim3(gg), dim3(256), 0, stream, arena, arena_len, (const uint4*)desc, n, out, status,
+                               flags_override, arena_w, low_grid);
+            return true;
+        },
+        verify, AmongBool{}, nt, AmongBool{});
     return hipGetLastError();
 }
 
 hipError_t launch_csum(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, uint32_t n,
-                       uint32_t* out, uint8_t* status, const uint8_t* flags_override, uint32_t mode,
-                       uint8_t* arena_w, int team_log2, int grid_override, hipStream_t stream) {
+                       uint32_t* out, uint8_t* status, const uint8_t* flags_override, bool verify,
+                       uint8_t* arena_w, const CsumTune& tune, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const bool verify = (mode & VPCSUM_MODE_VERIFY) != 0;
-    const int grid = grid_override;   // <= 0: each launcher's default
-    // mode bit 13 (internal tuning): plain loads instead of non-temporal ones
-    const bool nt = (mode & 0x2000u) == 0;
-    // mode bit 14 (internal tuning): K2 without the sampled low-concurrency grid
-    const bool adapt = (mode & 0x4000u) == 0;
-    // variant = (lanes per packet, chunks in flight per lane); ids 2..6 are log2(lanes)
+    const bool nt = tune.nt, adapt = tune.adapt;
+    int grid = 0;   // <= 0: each launcher's default
+    if (tune.wgs_per_cu) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        grid = num_cus(dev) * (int)tune.wgs_per_cu;
+    }
+    // the team kernel (K1): lanes per packet, chunks in flight per lane
 #define VPC_T(T, U) launch_team<T, U>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, \
                                       grid > 0 ? grid : (int)default_grid(), stream)
-    switch (team_log2) {
-        case 2: return VPC_T(4, 4);
+    // K2: one named build
+    auto k2 = [&](auto build) {
+        return launch_d<decltype(build)>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid,
+                                         adapt, stream);
+    };
+    switch (tune.variant) {
+        case 2: return VPC_T(4, 4);   // ids 2..6 are log2(lanes)
         case 3: return VPC_T(8, 4);
         case 4: return VPC_T(16, 8);
         case 5: return VPC_T(32, 4);
@@ -1705,49 +1728,41 @@ hipError_t launch_csum(const uint8_t* arena, uint64_t arena_len, const vpcsum_de
         // zero-copy frames in host memory: one wave per packet, predicated loads (k1_run PRED)
         case 12: return launch_team<64, 4, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt,
                                                  arena_w, grid > 0 ? grid : (int)default_grid(), stream);
-        case 40: return launch_d<8, 6>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 41: return launch_d<4, 12>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 43: return launch_d<16, 6>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 45: return launch_d<2, 12>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 46: return launch_d<8, 6, 2, 4>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 47: return launch_d<8, 6, 1, 4>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 48: return launch_d<8, 8, 2, 4>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 49: return launch_d<8, 6, 4, 4>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 50: return launch_d<8, 6, 2, 2>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 54: return launch_d<8, 4, 2, 2>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 58: return launch_d<8, 12, 2, 2>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 62: return launch_d<8, 6, 2, 2, 1, 1>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 66: return launch_d<8, 6, 2, 2, 1, 0, 1>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        // 70: the default; 72: the default without window units (A/B)
-        case 72: return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, false>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        case 74: return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-        // 76: the default without staged result stores (A/B)
-        case 76: return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, false>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
+        // tuning shapes: K2Build<TEAM, U, TS, US, WPE, IL, ROT>
+        case 40: return k2(K2Build<8, 6>{});
+        case 41: return k2(K2Build<4, 12>{});
+        case 43: return k2(K2Build<16, 6>{});
+        case 45: return k2(K2Build<2, 12>{});
+        case 46: return k2(K2Build<8, 6, 2, 4>{});
+        case 47: return k2(K2Build<8, 6, 1, 4>{});
+        case 48: return k2(K2Build<8, 8, 2, 4>{});
+        case 49: return k2(K2Build<8, 6, 4, 4>{});
+        case 50: return k2(K2Build<8, 6, 2, 2>{});
+        case 54: return k2(K2Build<8, 4, 2, 2>{});
+        case 58: return k2(K2Build<8, 12, 2, 2>{});
+        case 62: return k2(K2Build<8, 6, 2, 2, 1, 1>{});
+        case 66: return k2(K2Build<8, 6, 2, 2, 1, 0, 1>{});
+        // A/Bs on the default shape
+        case 72: return k2(K2NoWindowUnits{});
+        case 74: return k2(K2WtAB{});
+        case 76: return k2(K2NoStaging{});
         // 78: the team kernel with 64-bit loads, which serves arenas past 4 GiB (A/B, tooling)
-        case 78: return launch_team<kDefaultTeam, kDefaultUnroll>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid > 0 ? grid : (int)default_grid(), stream);
-        // 79: the staging build on every batch (round 3's r03w default, A/B)
-        case 79: return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
+        case 78: return VPC_T(kDefaultTeam, kDefaultUnroll);
+        case 79: return k2(K2StagedUnsorted{});
         // 84: the default for non-dense batches (the staging build with workgroup-sorted units on
-        // mixed batches); 79 is the same build without the workgroup sort
-        case 84:
-            if (arena_len > kMaxBufArena) return hipErrorInvalidValue;
-            return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, true, false, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
+        // mixed batches, k2_run WGS) on every batch below 4 GiB
+        case 84: return arena_len > kMaxBufArena ? hipErrorInvalidValue : k2(K2Staged{});
         case 70:
-        case 0:
-            // Arenas past 4 GiB: K2 with a pass per 2-GiB window its units' packets start in (see
-            // kWinBytes); not 16-B aligned: the team kernel (launch_d's fallback)
-            if (arena_len > kMaxBufArena) {
-                if (grid <= 0 && adapt && arena_len <= (uint64_t)n * 128u)
-                    return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, false, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-                return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, true, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-            }
+        case 0: {
             // Dense small frames (at most 128 arena bytes per packet: C1) never stage their result
-            // words: they take the build without staging and its smaller LDS
-            if (grid <= 0 && adapt && arena_len <= (uint64_t)n * 128u)
-                return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, false>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
-            // everything else: the staging build, whose mixed batches take workgroup-sorted units
-            // (k2_run WGS)
-            return launch_d<kDefaultTeam, kDefaultUnroll, kSmallTeam, kSmallUnroll, 1, 0, kDefaultRot, true, false, true, false, true>(arena, arena_len, desc, n, out, status, flags_override, verify, nt, arena_w, grid, adapt, stream);
+            // words: they take the build without staging and its smaller LDS;
+            // everything else the staging build, whose mixed batches take workgroup-sorted units.
+            // Arenas past 4 GiB: the same two with a pass per 2-GiB window their units' packets
+            // start in (see kWinBytes).  Not 16-B aligned: the team kernel (launch_d's fallback).
+            const bool dense = grid <= 0 && adapt && arena_len <= (uint64_t)n * 128u;
+            if (arena_len > kMaxBufArena) return dense ? k2(K2DenseWin{}) : k2(K2StagedWin{});
+            return dense ? k2(K2Dense{}) : k2(K2Staged{});
+        }
         default: return hipErrorInvalidValue;   // unknown kernel variant id
     }
 #undef VPC_T

@@ -22,9 +22,9 @@
 // rewrites of the 48-B entries that carry VPCSUM_NAT_TCP: sequence addend, flags, MSS clamp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "vpcsum.h"
 #include "internal.h"
+#include "launch_modes.h"
 #include "device_common.h"
 #include "pre_common.h"
 #include "tcp_rewrite.h"
@@ -254,8 +254,8 @@ __global__ __launch_bounds__(256) void k_nat(uint8_t* __restrict__ arena, uint64
 // in this lane's LDS slot, rewritten there with byte-addressed LDS ops (the window's offset
 // differs per packet), and the changed range is stored back as ONE run of dwordx4 / x2 / dword
 // stores (bytewise only where it would pass the packet end: the next bytes may be another
-// packet's).  W packets per lane and iteration keep W windows in flight.
-constexpr int kNatChunks = 6;                   // window: 96 B
+// packet's).  W packets per lane and iteration keep W windows in flight.  (The window is
+// kNatChunks chunks, launch_modes.h.)
 
 // Store back bytes [lo, hi) of the packet (relative to L3; the window holds it at w + r0, base is
 // the window's 16-B aligned global address) as one run of dwords, widest first, bytewise only
@@ -771,33 +771,24 @@ __global__ __launch_bounds__(256) void k_pre(uint8_t* __restrict__ arena, uint64
 }
 
 static uint32_t nat_grid(uint32_t n, int wl2, uint32_t wgs_per_cu);
-static uint32_t nat_wgs_per_cu(uint32_t nat_mode);
 
-hipError_t launch_pre(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* pre, int fmt, uint32_t n,
-                      uint32_t* out, uint8_t* status, uint32_t mode, hipStream_t stream) {
+hipError_t launch_pre(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* pre, uint32_t n,
+                      uint32_t* out, uint8_t* status, const PreBuild& b, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const int write = (mode & VPCSUM_MODE_WRITE) ? 1 : 0;
-    const int byte_path = (mode & 0x100u) ? 1 : 0;
-    // packets per lane: one by default (C5 +0.9% over two, profiles/r05d_presweep.json), bits 12..13 = 2: two
-    const int w1 = ((mode >> 12) & 3u) != 2;
-    const bool ch4 = ((mode >> 16) & 3u) == 2 && fmt == 0;       // 4-chunk windows (16-B entries only)
-    const bool probe = (mode & 0x800000u) != 0 && fmt == 0;
-    const int nt_store = (mode & 0x1000000u) ? 1 : 0;   // bit 24: non-temporal field stores (A/B)
-    const uint32_t g = nat_grid(n, w1 ? 0 : 1, nat_wgs_per_cu(mode));
+    const uint32_t g = nat_grid(n, b.wl2, b.wgs_per_cu);
     const uint4* d = (const uint4*)desc;
-#define VPC_PRE(F, W, C, P)                                                                                             \
-    hipLaunchKernelGGL((k_pre<F, W, C, P>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, pre, n, out, status, write, \
-                       byte_path, nt_store)
-    if (probe) {
-        if (ch4) VPC_PRE(0, 2, 4, true); else VPC_PRE(0, 2, kNatChunks, true);
-    } else if (fmt == 0) {
-        if (ch4) { if (w1) VPC_PRE(0, 1, 4, false); else VPC_PRE(0, 2, 4, false); }
-        else { if (w1) VPC_PRE(0, 1, kNatChunks, false); else VPC_PRE(0, 2, kNatChunks, false); }
-    } else {
-        if (w1) VPC_PRE(1, 1, kNatChunks, false); else VPC_PRE(1, 2, kNatChunks, false);
-    }
-#undef VPC_PRE
-    return hipGetLastError();
+    const bool known = dispatch(
+        [&](auto F, auto W, auto C, auto P) {
+            if constexpr (pre_exists(F, W, C, P)) {
+                hipLaunchKernelGGL((k_pre<F, W, C, P>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, pre, n, out,
+                                   status, b.write, b.byte_path, b.nt_store);
+                return true;
+            } else {
+                return false;
+            }
+        },
+        b.fmt, PreFmts{}, b.w, NatqPkts{}, b.ch, NatWindows{}, b.probe, AmongBool{});
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // Strict mode's status after the recompute kernel: that kernel reports a refused packet as
@@ -902,8 +893,6 @@ hipError_t launch_nat_tcp(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_
     return hipGetLastError();
 }
 
-constexpr int kNatWideLog2 = 1;   // packets per lane and iteration of k_natw: 2
-
 // Grid of the wide kernel: enough workgroups that one iteration of W packets per lane covers the
 // batch, capped at `wgs_per_cu` per CU (grid-stride beyond that).
 static uint32_t nat_grid(uint32_t n, int wl2, uint32_t wgs_per_cu) {
@@ -914,118 +903,54 @@ static uint32_t nat_grid(uint32_t n, int wl2, uint32_t wgs_per_cu) {
     return g > cap ? cap : g;
 }
 
-// Internal tuning bits of nat_mode (not part of the stable ABI): bit 8 byte-access kernel; bits
-// 12..14 log2(packets per lane) + 1 of the wide kernel (k_natw takes 1, 2 or 4 packets per lane;
-// k_natq only 1 or 2, so a request for 4 runs k_natq at 2); bits 16..17 window chunks (1: 6,
-// 2: 4); bits 18..22 workgroups per CU (0: 24); bit 23 the lane layout (k_natw) instead of quads
-// (k_natq); bits 24..25 k_natq's forced occupancy (1: 6, 2: 8 waves per SIMD -- tuning shapes that
-// may spill to scratch, tests/test_kernel_resources.py exempts them; 0 and 3: the default).
-static int nat_chunks_sel(uint32_t nat_mode, int fmt) {
-    const uint32_t c = (nat_mode >> 16) & 3u;
-    if (c == 1) return 6;
-    if (c == 2 && fmt != 1) return 4;
-    return kNatChunks;
-}
-// Default: 24 workgroups per CU (4 resident at 101 VGPRs, so the grid-stride loop starts in six
-// dispatch rounds): +2.6% over 8 on 10M C5 packets, 12 and 16 in between (profiles/r03e_nat_grid/)
-static uint32_t nat_wgs_per_cu(uint32_t nat_mode) {
-    const uint32_t w = (nat_mode >> 18) & 31u;
-    return w ? w : 24u;
-}
-
-hipError_t launch_nat_probe(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, int fmt,
-                            uint32_t n, hipStream_t stream) {
+// One rewrite kernel per NatBuild (launch_modes.h: nat_build decodes a nat_mode word, natq_exists /
+// natw_exists list the builds).  The pattern probes are builds with `probe`: status and flags_out
+// are NULL then.
+hipError_t launch_nat(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, uint32_t n,
+                      uint8_t* status, uint8_t* flags_out, const NatBuild& b, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    // tooling: the tuning bits of nat_mode, to price the same shapes launch_nat can take
-    static const uint32_t tune = [] {
-        const char* e = getenv("VPCSUM_NAT_PROBE_TUNE");
-        return e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
-    }();
-    const uint32_t g = nat_grid(n, kNatWideLog2, nat_wgs_per_cu(tune));
+    const uint32_t g = nat_grid(n, b.wl2, b.wgs_per_cu);
     const uint4* d = (const uint4*)desc;
-    constexpr int W = 1 << kNatWideLog2;
-    if (!(tune & 0x800000u)) {   // the quad layout (k_natq), as launch_nat's default
-        if (fmt == 2)
-            hipLaunchKernelGGL((k_natq<2, false, W, true>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                               (uint8_t*)nullptr, (uint8_t*)nullptr);
-        else if (fmt == 0 && nat_chunks_sel(tune, 0) == 4)
-            hipLaunchKernelGGL((k_natq<0, false, W, true, 4>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                               (uint8_t*)nullptr, (uint8_t*)nullptr);
-        else if (fmt == 0)
-            hipLaunchKernelGGL((k_natq<0, false, W, true>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                               (uint8_t*)nullptr, (uint8_t*)nullptr);
-        else
-            hipLaunchKernelGGL((k_natq<1, false, W, true>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                               (uint8_t*)nullptr, (uint8_t*)nullptr);
-    } else if (fmt == 0 && nat_chunks_sel(tune, 0) == 4)
-        hipLaunchKernelGGL((k_natw<0, false, W, true, 4>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                           (uint8_t*)nullptr, (uint8_t*)nullptr);
-    else if (fmt == 0)
-        hipLaunchKernelGGL((k_natw<0, false, W, true>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                           (uint8_t*)nullptr, (uint8_t*)nullptr);
-    else
-        hipLaunchKernelGGL((k_natw<1, false, W, true>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
-                           (uint8_t*)nullptr, (uint8_t*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_nat(uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const void* rw, int fmt,
-                      uint32_t n, uint8_t* status, uint8_t* flags_out, uint32_t nat_mode, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const bool strict = (nat_mode & VPCSUM_NAT_STRICT_JAVA) != 0;
-    const int wsel = (int)((nat_mode >> 12) & 7u);
-    const int wl2 = wsel ? (wsel - 1 > 2 ? 2 : wsel - 1) : kNatWideLog2;
-    const uint32_t g = nat_grid(n, wl2, nat_wgs_per_cu(nat_mode));
-    const int ch = nat_chunks_sel(nat_mode, fmt);
-    const bool wide = !(nat_mode & 0x100u);
-    const bool quad = (nat_mode & 0x800000u) == 0;
-    const uint4* d = (const uint4*)desc;
-    if (wide && quad) {
-#define VPC_NATQ(F, S, W, C)                                                                                           \
-    do {                                                                                                               \
-        const uint32_t wpe = (nat_mode >> 24) & 3u;                                                                    \
-        if (wpe == 1)                                                                                                  \
-            hipLaunchKernelGGL((k_natq<F, S, W, false, C, 6>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out); \
-        else if (wpe == 2)                                                                                             \
-            hipLaunchKernelGGL((k_natq<F, S, W, false, C, 8>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_natq<F, S, W, false, C>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out); \
-    } while (0)
-#define VPC_NATQ_W(F, S, C) do { if (wl2 == 0) VPC_NATQ(F, S, 1, C); else VPC_NATQ(F, S, 2, C); } while (0)
-        if (fmt == 2) {   // records: RFC 1624 only (the strict recompute takes plain descriptors)
-            if (ch == 4) VPC_NATQ_W(2, false, 4); else VPC_NATQ_W(2, false, kNatChunks);
-        } else if (fmt == 0 && ch == 4) {
-            if (strict) VPC_NATQ_W(0, true, 4); else VPC_NATQ_W(0, false, 4);
-        } else if (fmt == 0) {
-            if (strict) VPC_NATQ_W(0, true, kNatChunks); else VPC_NATQ_W(0, false, kNatChunks);
-        } else {
-            if (strict) VPC_NATQ_W(1, true, kNatChunks); else VPC_NATQ_W(1, false, kNatChunks);
-        }
-#undef VPC_NATQ_W
-#undef VPC_NATQ
-    } else if (wide) {
-#define VPC_NAT(F, S, W, C) hipLaunchKernelGGL((k_natw<F, S, W, false, C>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out)
-#define VPC_NAT_W(F, S) do { if (wl2 == 0) VPC_NAT(F, S, 1, kNatChunks); else if (wl2 == 1) VPC_NAT(F, S, 2, kNatChunks); else VPC_NAT(F, S, 4, kNatChunks); } while (0)
-        if (fmt == 2) {
-            VPC_NAT_W(2, false);
-        } else if (fmt == 0 && !strict && ch == 4) {
-            if (wl2 == 2) VPC_NAT(0, false, 4, 4); else VPC_NAT(0, false, 2, 4);
-        } else if (fmt == 0) {
-            if (strict) VPC_NAT_W(0, true); else VPC_NAT_W(0, false);
-        } else {
-            if (strict) VPC_NAT_W(1, true); else VPC_NAT_W(1, false);
-        }
-#undef VPC_NAT_W
-#undef VPC_NAT
-    } else if (fmt == 2) {
-        hipLaunchKernelGGL(k_nat<2>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out, 0);
-    } else if (fmt == 0) {
-        hipLaunchKernelGGL(k_nat<0>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out, strict ? 1 : 0);
-    } else {
-        hipLaunchKernelGGL(k_nat<1>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out, strict ? 1 : 0);
+    bool known = false;
+    switch (b.family) {
+        case NatFamily::Quad:
+            known = dispatch(
+                [&](auto F, auto S, auto W, auto P, auto C, auto WPE) {
+                    if constexpr (natq_exists(F, S, W, C, WPE, P)) {
+                        hipLaunchKernelGGL((k_natq<F, S, W, P, C, WPE>), dim3(g), dim3(256), 0, stream, arena, arena_len, d,
+                                           rw, n, status, flags_out);
+                        return true;
+                    } else {
+                        return false;
+                    }
+                },
+                b.fmt, NatFmts{}, b.strict, AmongBool{}, b.w, NatqPkts{}, b.probe, AmongBool{}, b.ch, NatWindows{}, b.wpe,
+                NatqOccupancies{});
+            break;
+        case NatFamily::Lane:
+            known = dispatch(
+                [&](auto F, auto S, auto W, auto P, auto C) {
+                    if constexpr (natw_exists(F, S, W, C, P)) {
+                        hipLaunchKernelGGL((k_natw<F, S, W, P, C>), dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n,
+                                           status, flags_out);
+                        return true;
+                    } else {
+                        return false;
+                    }
+                },
+                b.fmt, NatFmts{}, b.strict, AmongBool{}, b.w, NatwPkts{}, b.probe, AmongBool{}, b.ch, NatWindows{});
+            break;
+        case NatFamily::Byte:
+            known = !b.probe && dispatch(
+                [&](auto F) {
+                    hipLaunchKernelGGL(k_nat<F>, dim3(g), dim3(256), 0, stream, arena, arena_len, d, rw, n, status, flags_out,
+                                       b.strict ? 1 : 0);
+                    return true;
+                },
+                b.fmt, NatFmts{});
+            break;
     }
-    return hipGetLastError();
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
-
 
 }  // namespace vpcsum

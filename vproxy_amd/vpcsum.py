@@ -291,6 +291,13 @@ def _stream(stream) -> int | None:
 # ------------------------------------------------------------------------------------------
 # Device-resident API (torch CUDA tensors)
 # ------------------------------------------------------------------------------------------
+def _tune_bits(team_log2: int = 0, plain_loads: bool = False, blocks_per_cu: int = 0, full_grid: bool = False) -> int:
+    """The compute mode's tuning fields (csrc/launch_modes.h csum_bits; not part of the stable ABI):
+    kernel variant id, plain loads, workgroups per CU, no adaptive grid."""
+    return ((team_log2 & 0x1F) << 8) | (((team_log2 >> 5) & 0x7) << 24) | (0x2000 if plain_loads else 0) | \
+        (0x4000 if full_grid else 0) | ((blocks_per_cu & 0xFF) << 16)
+
+
 def compute(arena, desc, n: int | None = None, out=None, status=None, mode: int = MODE_COMPUTE,
             team_log2: int = 0, stream=None, plain_loads: bool = False, blocks_per_cu: int = 0,
             full_grid: bool = False):
@@ -298,7 +305,7 @@ def compute(arena, desc, n: int | None = None, out=None, status=None, mode: int 
     16-byte vpcsum_desc_t, `out` int32/uint32 tensor (n), `status` uint8 tensor (n)."""
     if n is None:
         n = desc.numel() * desc.element_size() // 16
-    m = mode | ((team_log2 & 0x1F) << 8) | (((team_log2 >> 5) & 0x7) << 24) | (0x2000 if plain_loads else 0) | (0x4000 if full_grid else 0) | ((blocks_per_cu & 0xFF) << 16)
+    m = mode | _tune_bits(team_log2, plain_loads, blocks_per_cu, full_grid)
     _check(lib().vpcsum_compute_async(_ptr(arena), arena.numel(), _ptr(desc), n, _ptr(out), _ptr(status), m,
                                       _stream(stream)), "vpcsum_compute_async")
 
@@ -411,7 +418,7 @@ class Pipe:
                 team_log2: int = 0):
         if n is None:
             n = desc.numel() * desc.element_size() // 16
-        m = mode | ((team_log2 & 0x1F) << 8) | (((team_log2 >> 5) & 0x7) << 24)
+        m = mode | _tune_bits(team_log2)
         _check(lib().vpcsum_pipe_compute_async(self.h, _ptr(arena), arena.numel(), _ptr(desc), n, _ptr(out),
                                                _ptr(status), m), "vpcsum_pipe_compute_async")
 
