@@ -6,11 +6,17 @@
 // decoders can reach against the builds the launchers instantiate (*_exists over the dispatchers'
 // candidate lists).  Stand-alone, plain g++ under ASan / UBSan; prints the build counts, which
 // tests/test_lib_cpu.py compares with the kernels in the code object.
+//
+// `launch_modes_test builds [FMT:WORD ...]` instead lists the NAT rewrite builds the launchers
+// instantiate (probes left out) and the build nat_build() resolves each given nat_mode word to, for
+// tests/test_lib_cpu.py to hold tests/natbuilds.py against.
+#include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <set>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -153,7 +159,56 @@ static std::vector<int> values(Among<T, Vs...>) {
     return {(int)Vs...};
 }
 
-int main() {
+// "exists F FMT STRICT W CH WPE" per non-probe build, then "resolves FMT WORD F FMT STRICT W CH WPE"
+// per argument.  The byte kernel takes `strict` as an argument: it has a strict build where
+// nat_build hands a strict request on to it.
+static int list_builds(int argc, char** argv) {
+    auto print = [](const char* what, const NatBuild& b) {
+        printf("%s %d %d %d %d %d %d\n", what, (int)b.family, b.fmt, (int)b.strict, b.w, b.ch, b.wpe);
+    };
+    for (int f : values(NatFmts{}))
+        for (int s : values(AmongBool{})) {
+            const NatBuild byte = nat_build(nat_bits::kBytePath | (s ? VPCSUM_NAT_STRICT_JAVA : 0u), f);
+            if (byte.family == NatFamily::Byte && byte.strict == (s != 0) && !byte.probe) print("exists", byte);
+            for (int c : values(NatWindows{})) {
+                for (int w : values(NatwPkts{}))
+                    if (natw_exists(f, s, w, c, false)) print("exists", NatBuild{NatFamily::Lane, f, s != 0, w, c, 1, false, 0, 0});
+                for (int w : values(NatqPkts{}))
+                    for (int o : values(NatqOccupancies{}))
+                        if (natq_exists(f, s, w, c, o, false))
+                            print("exists", NatBuild{NatFamily::Quad, f, s != 0, w, c, o, false, 0, 0});
+            }
+        }
+    for (int i = 2; i < argc; ++i) {
+        char* end = nullptr;
+        errno = 0;
+        const long fmt = strtol(argv[i], &end, 0);
+        if (errno || end == argv[i] || *end != ':' || fmt < 0 || fmt > 2) {
+            printf("bad argument %s\n", argv[i]);
+            return 2;
+        }
+        const char* ws = end + 1;
+        const unsigned long word = strtoul(ws, &end, 0);
+        if (errno || end == ws || *end || word > 0xfffffffful || (word & ~(unsigned long)kNatModeAccept)) {
+            printf("bad argument %s\n", argv[i]);
+            return 2;
+        }
+        char what[48];
+        snprintf(what, sizeof what, "resolves %ld 0x%lx", fmt, word);
+        print(what, nat_build((uint32_t)word, (int)fmt));
+    }
+    printf("builds ok\n");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) {
+        if (argv[1] != std::string("builds")) {
+            printf("usage: %s [builds [FMT:WORD ...]]\n", argv[0]);
+            return 2;
+        }
+        return list_builds(argc, argv);
+    }
     // the accept masks, bit for bit the literals api.cpp held
     CHECK(kCsumModeAccept == (0x07ff7fffu | 0x11u), "0x%x", kCsumModeAccept);
     CHECK(kNatModeAccept == (0x03u | 0x100u | 0x7000u | 0x3ff0000u), "0x%x", kNatModeAccept);

@@ -105,12 +105,55 @@ def test_batch_plan_under_sanitizers(tmp_path):
 
 
 @pytest.fixture(scope="module")
-def launch_modes_run(tmp_path_factory):
+def launch_modes_exe(tmp_path_factory):
     exe = tmp_path_factory.mktemp("launch_modes") / "launch_modes_test"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "vproxy_amd", "csrc"),
                            os.path.join(REPO, "tests", "cpp", "launch_modes_test.cpp"), "-o", str(exe)])
-    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    return str(exe)
+
+
+@pytest.fixture(scope="module")
+def launch_modes_run(launch_modes_exe):
+    return subprocess.run([launch_modes_exe], capture_output=True, text=True, timeout=120)
+
+
+def test_nat_build_table_is_the_header_list(launch_modes_exe):
+    """tests/natbuilds.py names every non-probe NAT rewrite build of launch_modes.h once per entry
+    format, nothing missing and nothing twice, and each of its nat_mode words resolves (nat_build)
+    to the build it stands next to: 70 builds today, 34 / 20 / 16 by format.  A build added to the
+    header without a word in the table -- so without a run against the oracle in
+    tests/test_gpu_nat_builds.py -- fails here.  The host program runs under ASan / UBSan."""
+    import natbuilds as NB
+    args = [f"{b.fmt}:{b.word():#x}" for b in NB.BUILDS]
+    r = subprocess.run([launch_modes_exe, "builds"] + args, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "builds ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    exists, resolves = [], []
+    for line in r.stdout.splitlines():
+        f = line.split()
+        if f[0] == "exists":
+            exists.append(tuple(int(x) for x in f[1:]))
+        elif f[0] == "resolves":
+            resolves.append((int(f[1]), int(f[2], 16), tuple(int(x) for x in f[3:])))
+    assert len(exists) == len(set(exists)), "the header's list names a build twice"
+    assert len(resolves) == len(NB.BUILDS)
+    for b, (fmt, w, got) in zip(NB.BUILDS, resolves):
+        assert (fmt, w) == (b.fmt, b.word()) and got == b.key, (b.id, hex(w), got)
+    keys = [b.key for b in NB.BUILDS]
+    assert len(set(keys)) == len(keys), "the table names a build twice"
+    assert len({b.id for b in NB.BUILDS}) == len(keys)
+    assert set(keys) == set(exists), (sorted(set(exists) - set(keys)), sorted(set(keys) - set(exists)))
+    by_fmt = {f: sum(1 for k in exists if k[1] == f) for f in (0, 1, 2)}
+    assert by_fmt == NB.COUNT_BY_FMT and len(exists) == 70, by_fmt
+    # the second-trip test's builds are in the table for both of its formats
+    for fam, w in NB.SECOND_TRIP:
+        for fmt in (NB.FMT_NAT4, NB.FMT_NAT):
+            assert NB.Build(fam, fmt, False, w, 0 if fam == "nat" else 6, 1) in NB.BUILDS
+    # the grid field changes the grid alone
+    r = subprocess.run([launch_modes_exe, "builds"] + [f"{b.fmt}:{b.word(wgs_per_cu=1):#x}" for b in NB.BUILDS],
+                       capture_output=True, text=True, timeout=120)
+    got = [tuple(int(x) for x in l.split()[3:]) for l in r.stdout.splitlines() if l.startswith("resolves")]
+    assert r.returncode == 0 and got == keys
 
 
 def test_launch_modes_under_sanitizers(launch_modes_run):
