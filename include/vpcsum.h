@@ -342,6 +342,53 @@ int vpcsum_parse_ether_hsum_async(const uint8_t* d_arena, uint64_t arena_len,
                                   uint8_t flags, vpcsum_desc_t* d_desc, uint8_t* d_status,
                                   vpcsum_hsum_t* d_hsum, void* stream);
 
+/* NAT flow table (additive, the ABI version stays 4): an exact-match table on one device from the
+ * tuple vpcsum_parse_ether_tuples_async writes -- conntrack.lookupTcp / lookupUdp's key (remote =
+ * the packet's source IPPort, local = its destination; Conntrack.java:106-125, TcpInput.java:47-51,
+ * UdpInput.java:45-47): protocol, both addresses, both ports, as received -- to the vpcsum_nat_t
+ * that SwitchUtils.applyNat writes for that flow direction (SwitchUtils.java:522-542).  The host
+ * inserts and erases flows at connection-setup rate; parse, lookup and rewrite of every packet
+ * stay on the device.  Only the stateless fast path is offloaded: in ESTABLISHED a TCP packet
+ * without FIN / SYN / RST gets resetTimer() and applyNat (executeTcpNat, SwitchUtils.java:318-459),
+ * a UDP packet always (executeUdpNat); every other packet of a known flow is handed back untouched
+ * (PUNT), and vpcsum_flowtab_collect tells the host which flows were hit (its resetTimer).
+ * INTEGRATION.md §5 has the vswitch's rule.  A table belongs to one device: there is no device
+ * group, process-wide or service-grid form. */
+#define VPCSUM_FLOW_MISS 0u /* no such flow, a refused frame (l3_ver 0), or not TCP / UDP           */
+#define VPCSUM_FLOW_HIT  1u /* found: the flow's entry is the packet's rewrite                      */
+#define VPCSUM_FLOW_PUNT 2u /* found, but TCP with FIN | SYN | RST (tcp_flags & 0x07): the host's   */
+typedef struct vpcsum_flow {
+    vpcsum_tuple_t key;   /* tcp_flags and rsv 0; an IPv4 address in the first 4 bytes, zeros after */
+    vpcsum_nat_t   rw;    /* the rewrite of every HIT packet of the flow                             */
+    uint64_t       cookie;/* the caller's name for the flow, returned by vpcsum_flowtab_collect      */
+} vpcsum_flow_t;          /* 96 bytes */
+typedef struct vpcsum_flowtab vpcsum_flowtab_t;
+
+/* A table for up to max_flows flows on `device` (slots: a power of two >= 2 x max_flows, 128 B each). */
+int vpcsum_flowtab_create(int device, uint32_t max_flows, vpcsum_flowtab_t** out);
+int vpcsum_flowtab_destroy(vpcsum_flowtab_t* tab);
+/* erase h_del[0..n_del) (a key not present is not an error), then insert / replace h_add[0..n_add)
+ * (a key already present keeps its flow and takes the new rw and cookie).
+ * The changed slots are copied on `stream` and the call returns after those copies completed:
+ * lookups queued on `stream` before the call see the old table, lookups after it the new one.
+ * A refused insert -- l4_proto other than 6 / 17, l3_ver other than 4 / 6, an IPv4 key with non-zero
+ * address bytes 4..15, non-zero tcp_flags / rsv, a full table -- fails the call with nothing changed. */
+int vpcsum_flowtab_update(vpcsum_flowtab_t* tab, const vpcsum_tuple_t* h_del, uint32_t n_del,
+                          const vpcsum_flow_t* h_add, uint32_t n_add, void* stream);
+/* slots, live flows, and the largest distance of a live flow from its home slot (any may be NULL) */
+int vpcsum_flowtab_info(vpcsum_flowtab_t* tab, uint32_t* slots, uint32_t* flows, uint32_t* max_probe);
+/* the table's hash of a key's 38 bytes (tcp_flags / rsv are not read): home slot = hash & (slots - 1) */
+int vpcsum_flow_hash(const vpcsum_tuple_t* key, uint64_t* out);
+/* Look n tuples up (device pointers, 4-byte aligned; d_rw n x vpcsum_nat_t, d_verdict n bytes):
+ * d_verdict[i] = VPCSUM_FLOW_*; d_rw[i] = the flow's entry on HIT, 48 zero bytes otherwise (mask 0:
+ * vpcsum_nat_async answers S_DONE and leaves the frame alone).  A HIT marks the flow for
+ * vpcsum_flowtab_collect.  On the table's device. */
+int vpcsum_flow_lookup_async(vpcsum_flowtab_t* tab, const vpcsum_tuple_t* d_tuples, uint32_t n,
+                             vpcsum_nat_t* d_rw, uint8_t* d_verdict, void* stream);
+/* cookies of the live flows that had a HIT since the last collect, each once; clears the marks.
+ * Synchronises `stream`. *n_out > cap: nothing cleared, call again with room. */
+int vpcsum_flowtab_collect(vpcsum_flowtab_t* tab, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream);
+
 /* Streaming-read ceiling probe: reads `bytes` from d_buf with 16-B lanes, writes one word per
  * block into d_sink.  Used by bench.py to report a measured HBM read roof next to 8 TB/s. */
 int vpcsum_read_probe_async(const uint8_t* d_buf, uint64_t bytes, uint32_t* d_sink,
@@ -474,6 +521,20 @@ int vpcsum_ctx_egress_frames(vpcsum_ctx_t* ctx, uint8_t* h_arena, uint64_t arena
 int vpcsum_ctx_nat_submit(vpcsum_ctx_t* ctx, uint8_t* h_arena, uint64_t arena_len,
                           const vpcsum_desc_t* h_desc, const vpcsum_nat_t* h_rw, uint32_t n,
                           uint8_t* h_status, uint32_t nat_mode, uint64_t* ticket);
+/* The NAT fast path of a received batch in one submission: the frames at h_frame_off[i]
+ * (h_frame_len[i] bytes) of a REGISTERED arena are parsed (vpcsum_parse_ether_tuples_async's rules),
+ * looked up in `tab` (vpcsum_flow_lookup_async) and rewritten in place with the entries found
+ * (nat_mode as vpcsum_ctx_nat_submit, VPCSUM_NAT_TCP_REWRITES included); tuples, entries and
+ * descriptors never leave the device.  At vpcsum_ctx_wait h_verdict[i] is VPCSUM_FLOW_* and
+ * h_status[i] S_DONE, or S_BAD_DESC (+ S_TTL_EXPIRED) for a frame the parse or the rewrite refuses,
+ * S_MSS_ABSENT next to S_DONE as vpcsum_nat_async sets it.  A frame with verdict MISS / PUNT or
+ * status S_BAD_DESC is left as it was: it takes the host's path.  An unregistered arena is refused
+ * (the frames' extents are unknown before the parse); the batch is launched also when the service
+ * grid is on.  tab must live on the context's device; a HIT marks its flow as vpcsum_flow_lookup_async
+ * does (the context's stream: call vpcsum_ctx_wait before vpcsum_flowtab_collect). */
+int vpcsum_ctx_nat_flow_frames(vpcsum_ctx_t* ctx, vpcsum_flowtab_t* tab, uint8_t* h_arena, uint64_t arena_len,
+                               const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n,
+                               uint8_t* h_status, uint8_t* h_verdict, uint32_t nat_mode, uint64_t* ticket);
 /* The egress flush of a batch holding NAT'd frames: vpcsum_ctx_submit where
  * descriptors with VPCSUM_F_PRE take their L4 sum from h_pre[i] (pre_fmt as vpcsum_pre_async;
  * entries of other descriptors are ignored) and the others are summed in full, in one submission.
@@ -610,6 +671,25 @@ int Java_io_vproxy_vpcsum_VPCsum_submitPre(PNIEnv_vpcsum_long* env, int64_t ctx,
  *                  MemorySegment rw, int n, MemorySegment status, int natMode) -> long ticket */
 int Java_io_vproxy_vpcsum_VPCsum_natSubmit(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen,
                                            void* desc, void* rw, int32_t n, void* status, int32_t natMode);
+/* VPCsum.flowtabCreate(int device, int maxFlows) -> long tab */
+int Java_io_vproxy_vpcsum_VPCsum_flowtabCreate(PNIEnv_vpcsum_long* env, int32_t device, int32_t maxFlows);
+/* VPCsum.flowtabUpdate(long tab, MemorySegment del, int nDel, MemorySegment add, int nAdd): 40-B
+ * vpcsum_tuple_t keys to erase, 96-B vpcsum_flow_t flows to insert / replace; returns when the
+ * device table holds them (vpcsum_flowtab_update, stream NULL: a natFlowFrames batch still in flight
+ * is not ordered against it -- waitFor it first; batches submitted afterwards see the new table) */
+int Java_io_vproxy_vpcsum_VPCsum_flowtabUpdate(PNIEnv_vpcsum_void* env, int64_t tab, void* del, int32_t nDel, void* add,
+                                               int32_t nAdd);
+/* VPCsum.flowtabCollect(long tab, MemorySegment cookies, int cap) -> int count (vpcsum_flowtab_collect;
+ * count > cap: nothing cleared) */
+int Java_io_vproxy_vpcsum_VPCsum_flowtabCollect(PNIEnv_vpcsum_int* env, int64_t tab, void* cookies, int32_t cap);
+/* VPCsum.flowtabClose(long tab) */
+int Java_io_vproxy_vpcsum_VPCsum_flowtabClose(PNIEnv_vpcsum_void* env, int64_t tab);
+/* VPCsum.natFlowFrames(long ctx, long tab, MemorySegment arena, long arenaLen, MemorySegment frameOff,
+ *                      MemorySegment frameLen, int n, MemorySegment status, MemorySegment verdict,
+ *                      int natMode) -> long ticket (vpcsum_ctx_nat_flow_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_natFlowFrames(PNIEnv_vpcsum_long* env, int64_t ctx, int64_t tab, void* arena,
+                                               int64_t arenaLen, void* frameOff, void* frameLen, int32_t n, void* status,
+                                               void* verdict, int32_t natMode);
 /* VPCsum.setService(long ctx, int idleUs) */
 int Java_io_vproxy_vpcsum_VPCsum_setService(PNIEnv_vpcsum_void* env, int64_t ctx, int32_t idleUs);
 /* VPCsum.waitFor(long ctx, long ticket) */

@@ -365,6 +365,23 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * The NAT fast path of a received batch (XDPIface.readable, then TcpInput / UdpInput's conntrack
+     * lookup and SwitchUtils.applyNat) without a per-packet step on the host: {@code count} frames at
+     * umem offsets {@code frameOff} (u64) with lengths {@code frameLen} (u32) are parsed, looked up
+     * in the flow table {@code tab} (VPCsum.flowtabCreate / flowtabUpdate) and rewritten in place.
+     * Fills {@code verdictOut} (VPCsum.FLOW_* per frame) and {@code statusOut}; a frame with
+     * FLOW_MISS / FLOW_PUNT or S_BAD_DESC is untouched and goes on to TcpInput / UdpInput as today.
+     * Afterwards VPCsum.flowtabCollect names the entries to resetTimer() (INTEGRATION.md §5).
+     */
+    public MemorySegment natFlow(long tab, MemorySegment frameOff, MemorySegment frameLen, int count, boolean strictJava,
+                                 MemorySegment statusOut, MemorySegment verdictOut) throws IOException {
+        long t = VPCsum.get().natFlowFrames(env, ctx, tab, umem, umemLen, frameOff, frameLen, count, statusOut, verdictOut,
+            strictJava ? VPCsum.NAT_STRICT_JAVA : VPCsum.NAT_RFC1624);
+        VPCsum.get().waitFor(env, ctx, t);
+        return verdictOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

@@ -368,7 +368,120 @@ public class VPCsum {
         return ENV.returnLong();
     }
 
-    private static final MethodHandle setServiceMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+    /** Verdicts of {@link #natFlowFrames} (VPCSUM_FLOW_*): no such flow (or not TCP / UDP, or a frame
+     * the parser refuses); rewritten with the flow's entry; known flow but TCP with FIN / SYN / RST. */
+    public static final int FLOW_MISS = 0, FLOW_HIT = 1, FLOW_PUNT = 2;
+    /** sizeof(vpcsum_flow_t): key (40-byte vpcsum_tuple_t, tcp_flags / rsv 0), rw (48-byte vpcsum_nat_t), cookie (u64). */
+    public static final int FLOW_BYTES = 96;
+
+    private static final MethodHandle flowtabCreateMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_flowtabCreate", int.class /* device */, int.class /* maxFlows */);
+
+    /** A NAT flow table for up to {@code maxFlows} flows on {@code device}: the part of Conntrack's
+     * lookup (Conntrack.java:106-125) the vswitch offloads (INTEGRATION.md §5). */
+    public long flowtabCreate(PNIEnv ENV, int device, int maxFlows) throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) flowtabCreateMH.invokeExact(ENV.MEMORY, device, maxFlows);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    private static final MethodHandle flowtabUpdateMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_flowtabUpdate", long.class /* tab */, MemorySegment.class /* del */, int.class /* nDel */,
+        MemorySegment.class /* add */, int.class /* nAdd */);
+
+    /** Erase the {@code nDel} keys of {@code del} (40 B each), then insert / replace the {@code nAdd}
+     * flows of {@code add} (FLOW_BYTES each).  Returns when the device table holds them; a refused
+     * flow (malformed key, full table) throws and changes nothing.  Wait for natFlowFrames batches
+     * in flight first: they are not ordered against the update. */
+    public void flowtabUpdate(PNIEnv ENV, long tab, MemorySegment del, int nDel, MemorySegment add, int nAdd)
+        throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) flowtabUpdateMH.invokeExact(ENV.MEMORY, tab, del, nDel, add, nAdd);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+    }
+
+    private static final MethodHandle flowtabCollectMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_flowtabCollect", long.class /* tab */, MemorySegment.class /* cookies */, int.class /* cap */);
+
+    /** The cookies (u64 each, room for {@code cap}) of the flows hit since the last collect, each
+     * once: the entries to resetTimer().  Returns their number; above {@code cap} nothing was
+     * written or cleared: call again with room. */
+    public int flowtabCollect(PNIEnv ENV, long tab, MemorySegment cookies, int cap) throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) flowtabCollectMH.invokeExact(ENV.MEMORY, tab, cookies, cap);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnInt();
+    }
+
+    private static final MethodHandle flowtabCloseMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_flowtabClose", long.class /* tab */);
+
+    public void flowtabClose(PNIEnv ENV, long tab) {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) flowtabCloseMH.invokeExact(ENV.MEMORY, tab);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwLast();
+        }
+    }
+
+    private static final MethodHandle natFlowFramesMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_natFlowFrames", long.class /* ctx */, long.class /* tab */, MemorySegment.class /* arena */,
+        long.class /* arenaLen */, MemorySegment.class /* frameOff */, MemorySegment.class /* frameLen */, int.class /* n */,
+        MemorySegment.class /* status */, MemorySegment.class /* verdict */, int.class /* natMode */);
+
+    /** The NAT fast path of a received batch of the registered umem in one submission: parse
+     * ({@link #parseFrames}' rules), lookup in {@code tab}, rewrite in place ({@link #natSubmit}'s
+     * natMode).  After {@link #waitFor}: verdict[i] FLOW_*, status[i] S_DONE / S_BAD_DESC
+     * (+ S_TTL_EXPIRED, S_MSS_ABSENT).  A frame with FLOW_MISS / FLOW_PUNT or S_BAD_DESC is
+     * untouched and takes TcpInput / UdpInput's path. */
+    public long natFlowFrames(PNIEnv ENV, long ctx, long tab, MemorySegment arena, long arenaLen, MemorySegment frameOff,
+                              MemorySegment frameLen, int n, MemorySegment status, MemorySegment verdict, int natMode)
+        throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) natFlowFramesMH.invokeExact(ENV.MEMORY, ctx, tab, arena, arenaLen, frameOff, frameLen, n, status, verdict, natMode);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    private static final MethodHandle setServiceMH =PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
         "Java_io_vproxy_vpcsum_VPCsum_setService", long.class /* ctx */, int.class /* idleUs */);
 
     /** Low-latency flushes: batches of up to 512 packets from a registered arena go to a resident

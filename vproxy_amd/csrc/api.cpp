@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "batch_plan.h"
+#include "flow_table.h"
 #include "internal.h"
 #include "vpcsum.h"
 
@@ -140,6 +141,7 @@ struct Batch {
     vpcsum_desc_t* user_desc_out = nullptr;   // parse batch: where descriptors and tuples go
     vpcsum_tuple_t* user_tuples = nullptr;
     vpcsum_hsum_t* user_hsum = nullptr;       // verify batch with header sums: where they go
+    uint8_t* user_verdict = nullptr;          // flow batch (vpcsum_ctx_nat_flow_frames): where the verdicts go
 };
 
 // Per-slot staging of one in-flight batch of a context.
@@ -158,6 +160,8 @@ struct Slot {
     vpcsum_nat_t* d_rw = nullptr;      // context's first NAT batch
     Mapped<vpcsum_tuple_t> h_tu;       // flow tuples of a parse batch: with the context's first parse batch
     Mapped<vpcsum_hsum_t> h_hs;        // ingress header sums of a verify batch: with the first such batch
+    vpcsum_tuple_t* d_tu = nullptr;    // a flow batch's tuples (parse -> lookup, device only) and its verdicts:
+    Mapped<uint8_t> h_verdict;         // with the context's first flow batch
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool busy = false;                 // `batch` is in flight
@@ -683,6 +687,8 @@ static void slot_free(Slot& s) {
     if (s.d_rw) (void)hipFree(s.d_rw);
     s.h_tu.free();
     s.h_hs.free();
+    if (s.d_tu) (void)hipFree(s.d_tu);
+    s.h_verdict.free();
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = Slot();
@@ -963,6 +969,7 @@ static int slot_finish(vpcsum_ctx* c, Slot& s) {
     const uint8_t* res_status = svc ? c->svc.h_status.p : s.h_status.p;
     const uint8_t* aux = c->svc.h_pre.p;
     if (b.user_status) memcpy(b.user_status, res_status, b.n);
+    if (b.user_verdict) memcpy(b.user_verdict, s.h_verdict.p, b.n);
     switch (b.kind) {
     case BatchKind::Nat:
         // a staged batch's rewritten headers (L3 header through the L4 checksum field; the TCP
@@ -1348,7 +1355,7 @@ int vpcsum_ctx_wait(vpcsum_ctx_t* c, uint64_t ticket) {
 template <class Body>
 static int frames_entry(vpcsum_ctx* c, const char* what, const char* nulls, const uint8_t* h_arena, uint64_t arena_len,
                         const uint64_t* h_frame_off, const uint32_t* h_frame_len, const void* also, uint32_t n,
-                        uint64_t* ticket, Body body) {
+                        uint64_t* ticket, Body body, bool may_svc = true) {
     if (!c || !ticket) return fail("%s: NULL context or ticket", what);
     if (n > c->max_pkts) return fail("%s: %u frames > capacity %u", what, n, c->max_pkts);
     if (n && (!h_arena || !h_frame_off || !h_frame_len || !also)) return fail("%s: NULL %s", what, nulls);
@@ -1361,7 +1368,7 @@ static int frames_entry(vpcsum_ctx* c, const char* what, const char* nulls, cons
     if (!s) return -1;
     b.n = n;
     b.zero_copy = true;   // read, and written, in place through the mapping
-    const bool svc = n && c->svc.on && n <= kSvcBatchMax;
+    const bool svc = may_svc && n && c->svc.on && n <= kSvcBatchMax;
     if (n && !svc) {
         memcpy(s->h_foff.p, h_frame_off, (size_t)n * 8);
         memcpy(s->h_flen.p, h_frame_len, (size_t)n * 4);
@@ -1532,6 +1539,242 @@ int vpcsum_ctx_nat_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
         }
         return slot_commit(s, b, ticket);
     } VPC_CATCH("vpcsum_ctx_nat_submit")
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// NAT flow table (vpcsum.h vpcsum_flowtab_*): the host logic is flow_table.h's FlowTable over a
+// pinned mirror of the device table; an update changes the mirror, copies the slots it dirtied (in
+// runs of neighbours) on the caller's stream and waits for them, so the mirror is never written
+// while a copy reads it.  `touched` is one byte per flow id, set by the lookup kernel.
+// ------------------------------------------------------------------------------------------
+struct vpcsum_flowtab {
+    int device = 0;
+    uint32_t max_flows = 0;
+    FlowSlot* h_slots = nullptr;    // pinned mirror
+    FlowSlot* d_slots = nullptr;
+    uint8_t* d_touched = nullptr;   // max_flows bytes
+    uint8_t* h_touched = nullptr;   // pinned, collect's copy
+    std::unique_ptr<FlowTable> t;
+    bool resync = false;            // a copy of changed slots failed: the next update copies the whole table
+    std::mutex mu;
+};
+
+static void flowtab_free(vpcsum_flowtab* f) {
+    if (f->h_slots) (void)hipHostFree(f->h_slots);
+    if (f->d_slots) (void)hipFree(f->d_slots);
+    if (f->d_touched) (void)hipFree(f->d_touched);
+    if (f->h_touched) (void)hipHostFree(f->h_touched);
+    delete f;
+}
+
+// [a, b) runs of consecutive values in the sorted, duplicate-free v
+template <class F>
+static int for_runs(const std::vector<uint32_t>& v, F f) {
+    for (size_t i = 0; i < v.size();) {
+        size_t j = i + 1;
+        while (j < v.size() && v[j] == v[j - 1] + 1) ++j;
+        if (f(v[i], v[j - 1] + 1) != 0) return -1;
+        i = j;
+    }
+    return 0;
+}
+
+static void sort_unique(std::vector<uint32_t>& v) {
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+}
+
+// The lookup of a batch on the table's device; caller holds f->mu (max_probe and the launch are one
+// step against a concurrent update).
+static int flow_lookup_locked(vpcsum_flowtab* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
+                              uint8_t* d_verdict, hipStream_t s) {
+    VPC_CHECK(launch_flow_lookup(f->d_slots, f->t->mask(), f->t->max_probe(), f->d_touched, d_tuples, n, d_rw, d_verdict, s),
+              "flow lookup launch");
+    return 0;
+}
+
+extern "C" {
+
+int vpcsum_flowtab_create(int device, uint32_t max_flows, vpcsum_flowtab_t** out) {
+    try {
+        if (!out) return fail("vpcsum_flowtab_create: out is NULL");
+        if (max_flows == 0 || max_flows > (1u << 24)) return fail("vpcsum_flowtab_create: max_flows %u outside 1..2^24", max_flows);
+        VPC_ON_DEVICE(device);
+        vpcsum_flowtab* f = new vpcsum_flowtab();
+        f->device = device;
+        f->max_flows = max_flows;
+        const size_t bytes = (size_t)FlowTable::slots_for(max_flows) * sizeof(FlowSlot);
+        hipError_t e = hipSuccess;
+        if ((e = hipHostMalloc((void**)&f->h_slots, bytes, 0)) != hipSuccess ||
+            (e = hipMalloc((void**)&f->d_slots, bytes)) != hipSuccess ||
+            (e = hipMalloc((void**)&f->d_touched, max_flows)) != hipSuccess ||
+            (e = hipHostMalloc((void**)&f->h_touched, max_flows, 0)) != hipSuccess ||
+            (e = hipMemset(f->d_slots, 0, bytes)) != hipSuccess || (e = hipMemset(f->d_touched, 0, max_flows)) != hipSuccess ||
+            (e = hipDeviceSynchronize()) != hipSuccess) {
+            flowtab_free(f);
+            return hipfail(e, "vpcsum_flowtab_create allocation");
+        }
+        memset((void*)f->h_slots, 0, bytes);
+        try {
+            f->t.reset(new FlowTable(max_flows, f->h_slots));
+        } catch (...) {
+            flowtab_free(f);
+            throw;
+        }
+        *out = f;
+        return 0;
+    } VPC_CATCH("vpcsum_flowtab_create")
+}
+
+int vpcsum_flowtab_destroy(vpcsum_flowtab_t* f) {
+    try {
+        if (!f) return 0;
+        DeviceScope on_dev(f->device);
+        (void)hipDeviceSynchronize();   // lookups still reading the table finish first
+        flowtab_free(f);
+        return 0;
+    } VPC_CATCH("vpcsum_flowtab_destroy")
+}
+
+int vpcsum_flowtab_update(vpcsum_flowtab_t* f, const vpcsum_tuple_t* h_del, uint32_t n_del, const vpcsum_flow_t* h_add,
+                          uint32_t n_add, void* stream) {
+    try {
+        if (!f) return fail("vpcsum_flowtab_update: NULL table");
+        if ((n_del && !h_del) || (n_add && !h_add)) return fail("vpcsum_flowtab_update: NULL keys or flows");
+        std::lock_guard<std::mutex> lk(f->mu);
+        VPC_ON_DEVICE(f->device);
+        std::string why;
+        if (!f->t->validate(h_del, n_del, h_add, n_add, &why)) return fail("vpcsum_flowtab_update: %s", why.c_str());
+        // room for the bookkeeping before the table changes: nothing below refuses (validated) or
+        // allocates (FlowTable, FlowDirty), so the mirror is never left half changed
+        FlowDirty dirty((size_t)n_del * 4 + n_add + 16);
+        std::vector<uint32_t> freed;
+        freed.reserve(n_del);
+        for (uint32_t i = 0; i < n_del; ++i) {
+            const int64_t id = f->t->erase(h_del[i], &dirty);
+            if (id >= 0) freed.push_back((uint32_t)id);
+        }
+        for (uint32_t i = 0; i < n_add; ++i) (void)f->t->insert(h_add[i], &dirty);
+        sort_unique(dirty.idx);
+        sort_unique(freed);
+        // the whole table in one copy instead of its runs: a bulk load (an eighth of the slots or
+        // more changed), more slots written than `dirty` had room for, or an earlier copy that failed
+        const bool whole = dirty.all || f->resync || dirty.idx.size() >= f->t->slots() / 8u;
+        f->resync = true;   // until the copies below are queued
+        hipStream_t s = (hipStream_t)stream;
+        // an erased flow's mark goes with it: the id may be handed to another flow
+        int rc = for_runs(freed, [&](uint32_t a, uint32_t b) {
+            VPC_CHECK(hipMemsetAsync(f->d_touched + a, 0, b - a, s), "vpcsum_flowtab_update: clearing marks");
+            return 0;
+        });
+        auto copy_slots = [&](uint32_t a, uint32_t b) {
+            VPC_CHECK(hipMemcpyAsync(f->d_slots + a, f->h_slots + a, (size_t)(b - a) * sizeof(FlowSlot), hipMemcpyHostToDevice, s),
+                      "vpcsum_flowtab_update: H2D slots");
+            return 0;
+        };
+        if (rc == 0) rc = whole ? copy_slots(0, f->t->slots()) : for_runs(dirty.idx, copy_slots);
+        const hipError_t e = hipStreamSynchronize(s);   // also after a failed copy: none reads the mirror after the return
+        if (rc != 0) return -1;   // the mirror is ahead of the device: the next update copies everything (resync)
+        VPC_CHECK(e, "vpcsum_flowtab_update: hipStreamSynchronize");
+        f->resync = false;
+        return 0;
+    } VPC_CATCH("vpcsum_flowtab_update")
+}
+
+int vpcsum_flowtab_info(vpcsum_flowtab_t* f, uint32_t* slots, uint32_t* flows, uint32_t* max_probe) {
+    try {
+        if (!f) return fail("vpcsum_flowtab_info: NULL table");
+        std::lock_guard<std::mutex> lk(f->mu);
+        if (slots) *slots = f->t->slots();
+        if (flows) *flows = f->t->flows();
+        if (max_probe) *max_probe = f->t->max_probe();
+        return 0;
+    } VPC_CATCH("vpcsum_flowtab_info")
+}
+
+int vpcsum_flow_hash(const vpcsum_tuple_t* key, uint64_t* out) {
+    try {
+        if (!key || !out) return fail("vpcsum_flow_hash: NULL argument");
+        *out = flow_hash(*key);
+        return 0;
+    } VPC_CATCH("vpcsum_flow_hash")
+}
+
+int vpcsum_flow_lookup_async(vpcsum_flowtab_t* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
+                             uint8_t* d_verdict, void* stream) {
+    try {
+        if (!f) return fail("vpcsum_flow_lookup_async: NULL table");
+        if (n == 0) return 0;
+        if (!d_tuples || !d_rw || !d_verdict) return fail("vpcsum_flow_lookup_async: NULL tuples, entries or verdicts");
+        if (((uintptr_t)d_tuples | (uintptr_t)d_rw) & 3) return fail("vpcsum_flow_lookup_async: tuples / entries not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_flow_lookup_async: %u packets > 2^28", n);
+        std::lock_guard<std::mutex> lk(f->mu);
+        VPC_ON_DEVICE(f->device);
+        return flow_lookup_locked(f, d_tuples, n, d_rw, d_verdict, (hipStream_t)stream);
+    } VPC_CATCH("vpcsum_flow_lookup_async")
+}
+
+int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream) {
+    try {
+        if (!f || !n_out) return fail("vpcsum_flowtab_collect: NULL table or count");
+        if (cap && !h_cookies) return fail("vpcsum_flowtab_collect: NULL cookies");
+        std::lock_guard<std::mutex> lk(f->mu);
+        VPC_ON_DEVICE(f->device);
+        hipStream_t s = (hipStream_t)stream;
+        VPC_CHECK(hipMemcpyAsync(f->h_touched, f->d_touched, f->max_flows, hipMemcpyDeviceToHost, s), "vpcsum_flowtab_collect: D2H marks");
+        VPC_CHECK(hipStreamSynchronize(s), "vpcsum_flowtab_collect: hipStreamSynchronize");
+        uint32_t cnt = 0;
+        for (uint32_t id = 0; id < f->max_flows; ++id) cnt += (f->h_touched[id] && f->t->live(id)) ? 1u : 0u;
+        *n_out = cnt;
+        if (cnt > cap) return 0;   // nothing cleared: the caller comes back with room
+        uint32_t k = 0;
+        for (uint32_t id = 0; id < f->max_flows; ++id)
+            if (f->h_touched[id] && f->t->live(id)) h_cookies[k++] = f->t->cookie(id);
+        if (cnt) VPC_CHECK(hipMemsetAsync(f->d_touched, 0, f->max_flows, s), "vpcsum_flowtab_collect: clearing marks");
+        return 0;
+    } VPC_CATCH("vpcsum_flowtab_collect")
+}
+
+int vpcsum_ctx_nat_flow_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uint8_t* h_arena, uint64_t arena_len,
+                               const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n, uint8_t* h_status,
+                               uint8_t* h_verdict, uint32_t nat_mode, uint64_t* ticket) {
+    try {
+        const char* what = "vpcsum_ctx_nat_flow_frames";
+        if (!f) return fail("%s: NULL flow table", what);
+        if (c && f->device != c->device)
+            return fail("%s: the flow table lives on device %d, the context on device %d", what, f->device, c->device);
+        if (nat_mode & ~kNatCtxModeAccept) return fail("%s: bad nat_mode 0x%x", what, nat_mode);
+        if (n && !h_verdict) return fail("%s: NULL verdicts", what);
+        // the service grid has no lookup: the batch is launched whatever its size (may_svc false)
+        return frames_entry(c, what, "arena, frame table or status", h_arena, arena_len, h_frame_off, h_frame_len, h_status, n,
+                            ticket, [&](Slot& s, Batch b, uint8_t* base, bool) {
+            b.kind = BatchKind::Nat;   // zero-copy: the frames are rewritten where they lie
+            b.mode = nat_mode;
+            b.user_status = h_status;
+            b.user_verdict = h_verdict;
+            if (n) {
+                // per-packet scratch of the chain, sized from max_pkts with the context's first such
+                // batch: tuples and entries on the device, verdicts in pinned memory
+                if (slot_rw_alloc(c, s, what) != 0) return -1;
+                if (!s.d_tu) VPC_CHECK(hipMalloc((void**)&s.d_tu, (size_t)c->max_pkts * sizeof(vpcsum_tuple_t)), what);
+                if (!s.h_verdict.p) VPC_CHECK(s.h_verdict.alloc(c->max_pkts), what);
+                // parse -> tuples -> lookup -> entries -> rewrite, one stream; the parse's status
+                // bytes are not needed: a refused frame's descriptor is all zeros, which the rewrite
+                // refuses (S_BAD_DESC, nothing written)
+                VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
+                                             nullptr, s.d_tu, s.stream),
+                          "parse launch");
+                {
+                    std::lock_guard<std::mutex> lf(f->mu);
+                    if (flow_lookup_locked(f, s.d_tu, n, s.d_rw, s.h_verdict.dev, s.stream) != 0) return -1;
+                }
+                if (nat_run(base, arena_len, s.d_desc, s.d_rw, 1, n, s.h_status.dev, nat_mode, s.stream) != 0) return -1;
+            }
+            return slot_commit(s, b, ticket);
+        }, false);
+    } VPC_CATCH("vpcsum_ctx_nat_flow_frames")
 }
 
 int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint32_t copy_bytes,
@@ -2103,6 +2346,63 @@ int Java_io_vproxy_vpcsum_VPCsum_natSubmit(PNIEnv_vpcsum_long* env, int64_t ctx,
         return vpcsum_ctx_nat_submit((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)arena, (uint64_t)arenaLen,
                                      (const vpcsum_desc_t*)desc, (const vpcsum_nat_t*)rw, (uint32_t)n, (uint8_t*)status,
                                      (uint32_t)natMode, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_flowtabCreate(PNIEnv_vpcsum_long* env, int32_t device, int32_t maxFlows) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_flowtabCreate", maxFlows <= 0, "maxFlows must be positive",
+                         [&](uint64_t* handle) {
+        vpcsum_flowtab_t* f = nullptr;
+        const int rc = vpcsum_flowtab_create(device, (uint32_t)maxFlows, &f);
+        *handle = (uint64_t)(uintptr_t)f;
+        return rc;
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_flowtabUpdate(PNIEnv_vpcsum_void* env, int64_t tab, void* del, int32_t nDel, void* add,
+                                               int32_t nAdd) {
+    try {
+        if (nDel < 0 || nAdd < 0) {
+            fail("flowtabUpdate: negative count");
+            return pni_throw(env, "java.lang.IllegalArgumentException");
+        }
+        if (vpcsum_flowtab_update((vpcsum_flowtab_t*)(intptr_t)tab, (const vpcsum_tuple_t*)del, (uint32_t)nDel,
+                                  (const vpcsum_flow_t*)add, (uint32_t)nAdd, nullptr) != 0)
+            return pni_throw(env, "java.io.IOException");
+        return 0;
+    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_flowtabUpdate")
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_flowtabCollect(PNIEnv_vpcsum_int* env, int64_t tab, void* cookies, int32_t cap) {
+    try {
+        if (cap < 0) {
+            fail("flowtabCollect: negative capacity");
+            return pni_throw(env, "java.lang.IllegalArgumentException");
+        }
+        uint32_t cnt = 0;
+        if (vpcsum_flowtab_collect((vpcsum_flowtab_t*)(intptr_t)tab, (uint64_t*)cookies, (uint32_t)cap, &cnt, nullptr) != 0)
+            return pni_throw(env, "java.io.IOException");
+        env->return_ = (int32_t)cnt;
+        return 0;
+    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_flowtabCollect")
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_flowtabClose(PNIEnv_vpcsum_void* env, int64_t tab) {
+    try {
+        (void)env;
+        vpcsum_flowtab_destroy((vpcsum_flowtab_t*)(intptr_t)tab);
+        return 0;
+    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_flowtabClose")
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_natFlowFrames(PNIEnv_vpcsum_long* env, int64_t ctx, int64_t tab, void* arena,
+                                               int64_t arenaLen, void* frameOff, void* frameLen, int32_t n, void* status,
+                                               void* verdict, int32_t natMode) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_natFlowFrames", n < 0 || arenaLen < 0,
+                         "natFlowFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_nat_flow_frames((vpcsum_ctx_t*)(intptr_t)ctx, (vpcsum_flowtab_t*)(intptr_t)tab, (uint8_t*)arena,
+                                          (uint64_t)arenaLen, (const uint64_t*)frameOff, (const uint32_t*)frameLen,
+                                          (uint32_t)n, (uint8_t*)status, (uint8_t*)verdict, (uint32_t)natMode, t);
     });
 }
 

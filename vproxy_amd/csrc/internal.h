@@ -96,6 +96,13 @@ hipError_t launch_parse_ether(const uint8_t* arena, uint64_t arena_len, const ui
                               uint8_t* status, vpcsum_tuple_t* tuples, hipStream_t stream,
                               const uint8_t* frame_flags = nullptr, vpcsum_hsum_t* hsum = nullptr);
 
+// NAT flow table lookup (flow.hip): tuples[i] looked up in `slots` (mask + 1 FlowSlot of
+// flow_table.h, probes of at most max_probe + 1 slots): verdict_out[i] = VPCSUM_FLOW_*, rw_out[i] the
+// flow's entry on a HIT and 48 zero bytes otherwise, touched[flow id] = 1 on a HIT.
+hipError_t launch_flow_lookup(const void* slots, uint32_t mask, uint32_t max_probe, uint8_t* touched,
+                              const vpcsum_tuple_t* tuples, uint32_t n, vpcsum_nat_t* rw_out, uint8_t* verdict_out,
+                              hipStream_t stream);
+
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t grid, hipStream_t stream);
 hipError_t launch_pattern_probe(const uint8_t* arena, uint64_t arena_len, const void* desc, uint32_t n, uint32_t* sink,
                                 uint32_t grid, hipStream_t stream);

@@ -45,6 +45,9 @@ TUPLE_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "u1", 2)
 # vpcsum_hsum_t: a received TCP / UDP frame's ingress header sum (l2_len 0: no record)
 HSUM_DTYPE = np.dtype([("sum", "<u2"), ("l4_len", "<u2"), ("hlen", "u1"), ("l4_proto", "u1"), ("l3_ver", "u1"),
                        ("l2_len", "u1")])
+# vpcsum_flow_t: one flow of the NAT flow table -- key (tcp_flags / rsv 0), rewrite, caller's cookie
+FLOW_DTYPE = np.dtype([("key", TUPLE_DTYPE), ("rw", NAT_DTYPE), ("cookie", "<u8")])
+FLOW_MISS, FLOW_HIT, FLOW_PUNT = 0, 1, 2
 
 # Every symbol include/vpcsum.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -71,6 +74,11 @@ EXPORTS = [
     "vpcsum_ctx_verify_frames_hsum", "vpcsum_parse_ether_hsum_async", "Java_io_vproxy_vpcsum_VPCsum_verifyFramesHsum",
     "vpcsum_spin_probe_async", "vpcsum_pipe_create", "vpcsum_pipe_begin", "vpcsum_pipe_compute_async",
     "vpcsum_pipe_join", "vpcsum_pipe_destroy",
+    "vpcsum_flowtab_create", "vpcsum_flowtab_destroy", "vpcsum_flowtab_update", "vpcsum_flowtab_info",
+    "vpcsum_flow_hash", "vpcsum_flow_lookup_async", "vpcsum_flowtab_collect", "vpcsum_ctx_nat_flow_frames",
+    "Java_io_vproxy_vpcsum_VPCsum_flowtabCreate", "Java_io_vproxy_vpcsum_VPCsum_flowtabUpdate",
+    "Java_io_vproxy_vpcsum_VPCsum_flowtabCollect", "Java_io_vproxy_vpcsum_VPCsum_flowtabClose",
+    "Java_io_vproxy_vpcsum_VPCsum_natFlowFrames",
 ]
 
 
@@ -235,6 +243,14 @@ def _declare(L):
         "vpcsum_ctx_submit": ([P, P, U64, P, U32, P, P, U32, P], I),
         "vpcsum_ctx_wait": ([P, U64], I),
         "vpcsum_ctx_pipeline": ([P, P, U32, U32, P, U32, P, U32, U32], I),
+        "vpcsum_flowtab_create": ([I, U32, P], I),
+        "vpcsum_flowtab_destroy": ([P], I),
+        "vpcsum_flowtab_update": ([P, P, U32, P, U32, P], I),
+        "vpcsum_flowtab_info": ([P, P, P, P], I),
+        "vpcsum_flow_hash": ([P, P], I),
+        "vpcsum_flow_lookup_async": ([P, P, U32, P, P, P], I),
+        "vpcsum_flowtab_collect": ([P, P, U32, P, P], I),
+        "vpcsum_ctx_nat_flow_frames": ([P, P, P, U64, P, P, U32, P, P, U32, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -461,6 +477,72 @@ class Event:
             pass
 
 
+def flow_hash(key) -> int:
+    """vpcsum_flow_hash of one TUPLE_DTYPE key (tcp_flags / rsv are not read): a table of `slots`
+    slots keeps the key at or after slot hash & (slots - 1)."""
+    k = np.ascontiguousarray(np.asarray(key, TUPLE_DTYPE).reshape(1))
+    h = ctypes.c_uint64()
+    _check(lib().vpcsum_flow_hash(k.ctypes.data, ctypes.byref(h)), "vpcsum_flow_hash")
+    return h.value
+
+
+class FlowTable:
+    """The NAT flow table on one device (vpcsum_flowtab_*): TUPLE_DTYPE key -> NAT_DTYPE rewrite,
+    updated from the host, looked up on the GPU (lookup, Context.nat_flow_frames)."""
+
+    def __init__(self, max_flows: int, device: int = 0):
+        h = ctypes.c_void_p()
+        _check(lib().vpcsum_flowtab_create(device, max_flows, ctypes.byref(h)), "vpcsum_flowtab_create")
+        self.h = h.value
+        self.device = device
+
+    def update(self, delete=None, add=None, stream=None):
+        """Erase the TUPLE_DTYPE keys `delete`, then insert / replace the FLOW_DTYPE flows `add`;
+        returns once the device table holds them (ordered on `stream`).  A refused flow raises and
+        changes nothing."""
+        d = np.zeros(0, TUPLE_DTYPE) if delete is None else np.ascontiguousarray(np.asarray(delete, TUPLE_DTYPE).reshape(-1))
+        a = np.zeros(0, FLOW_DTYPE) if add is None else np.ascontiguousarray(np.asarray(add, FLOW_DTYPE).reshape(-1))
+        _check(lib().vpcsum_flowtab_update(self.h, d.ctypes.data if len(d) else None, len(d),
+                                           a.ctypes.data if len(a) else None, len(a), _stream(stream)),
+               "vpcsum_flowtab_update")
+
+    def lookup(self, tuples, n: int, rw, verdict, stream=None):
+        """vpcsum_flow_lookup_async: `tuples` n x 40 bytes, `rw` n x 48 bytes and `verdict` n bytes,
+        uint8 device tensors."""
+        assert tuples.numel() * tuples.element_size() >= n * TUPLE_DTYPE.itemsize
+        assert rw.numel() * rw.element_size() >= n * NAT_DTYPE.itemsize and verdict.numel() >= n
+        _check(lib().vpcsum_flow_lookup_async(self.h, _ptr(tuples), n, _ptr(rw), _ptr(verdict), _stream(stream)),
+               "vpcsum_flow_lookup_async")
+
+    def collect(self, cap: int | None = None, stream=None):
+        """Cookies of the flows hit since the last collect (marks cleared).  With `cap`, a count
+        above it is returned as (count, None) and nothing is cleared."""
+        room = self.info()["flows"] if cap is None else cap
+        out = np.zeros(max(room, 1), np.uint64)
+        n = ctypes.c_uint32()
+        _check(lib().vpcsum_flowtab_collect(self.h, out.ctypes.data, room, ctypes.byref(n), _stream(stream)),
+               "vpcsum_flowtab_collect")
+        if cap is None:
+            return out[:n.value].copy()
+        return n.value, (out[:n.value].copy() if n.value <= cap else None)
+
+    def info(self) -> dict:
+        s, f, m = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().vpcsum_flowtab_info(self.h, ctypes.byref(s), ctypes.byref(f), ctypes.byref(m)), "vpcsum_flowtab_info")
+        return {"slots": s.value, "flows": f.value, "max_probe": m.value}
+
+    def close(self):
+        if self.h:
+            lib().vpcsum_flowtab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------------------------------
 # Host-memory API (what the Java binding drives)
 # ------------------------------------------------------------------------------------------
@@ -600,6 +682,23 @@ class Context:
         status = np.zeros(len(desc), np.uint8)
         self.wait(self.nat_submit(arena, desc, rw, status, nat_mode))
         return status
+
+    def nat_flow_frames(self, tab: "FlowTable", arena: np.ndarray, frame_off: np.ndarray, frame_len: np.ndarray,
+                        nat_mode: int = NAT_RFC1624):
+        """The NAT fast path of received frames in a registered arena (vpcsum_ctx_nat_flow_frames):
+        parsed, looked up in `tab` and rewritten in place on the GPU.  Returns (status, verdict)
+        per frame; a frame with verdict FLOW_MISS / FLOW_PUNT or status S_BAD_DESC is untouched."""
+        n = len(frame_off)
+        fo = np.ascontiguousarray(frame_off, dtype=np.uint64)
+        fl = np.ascontiguousarray(frame_len, dtype=np.uint32)
+        status = np.zeros(n, np.uint8)
+        verdict = np.zeros(n, np.uint8)
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_nat_flow_frames(self.h, tab.h, arena.ctypes.data, arena.nbytes, fo.ctypes.data,
+                                                fl.ctypes.data, n, status.ctypes.data, verdict.ctypes.data, nat_mode,
+                                                ctypes.byref(t)), "vpcsum_ctx_nat_flow_frames")
+        self.wait(t.value)
+        return status, verdict
 
     def set_service(self, idle_us: int):
         """Low-latency flushes from registered arenas (persistent service grid); 0 = off."""
