@@ -9,7 +9,8 @@
 //
 // `launch_modes_test builds [FMT:WORD ...]` instead lists the NAT rewrite builds the launchers
 // instantiate (probes left out) and the build nat_build() resolves each given nat_mode word to, for
-// tests/test_lib_cpu.py to hold tests/natbuilds.py against.
+// tests/test_lib_cpu.py to hold tests/natbuilds.py against.  `launch_modes_test prebuilds [FMT:WORD ...]`
+// does the same for the k_pre builds (probes included) and pre_build(), for tests/prebuilds.py.
 #include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -201,13 +202,42 @@ static int list_builds(int argc, char** argv) {
     return 0;
 }
 
-int main(int argc, char** argv) {
-    if (argc > 1) {
-        if (argv[1] != std::string("builds")) {
-            printf("usage: %s [builds [FMT:WORD ...]]\n", argv[0]);
+// "exists FMT W CH PROBE" per k_pre build (pre_exists over the dispatcher's candidates), then
+// "resolves FMT WORD FMT W CH PROBE WRITE BYTE_PATH NT_STORE" per argument (pre_build).
+static int list_pre_builds(int argc, char** argv) {
+    for (int f : values(PreFmts{}))
+        for (int w : values(NatqPkts{}))
+            for (int c : values(NatWindows{}))
+                for (int p : values(AmongBool{}))
+                    if (pre_exists(f, w, c, p != 0)) printf("exists %d %d %d %d\n", f, w, c, p);
+    for (int i = 2; i < argc; ++i) {
+        char* end = nullptr;
+        errno = 0;
+        const long fmt = strtol(argv[i], &end, 0);
+        if (errno || end == argv[i] || *end != ':' || fmt < 0 || fmt > 1) {
+            printf("bad argument %s\n", argv[i]);
             return 2;
         }
-        return list_builds(argc, argv);
+        const char* ws = end + 1;
+        const unsigned long word = strtoul(ws, &end, 0);
+        if (errno || end == ws || *end || word > 0xfffffffful || (word & ~(unsigned long)kPreModeAccept)) {
+            printf("bad argument %s\n", argv[i]);
+            return 2;
+        }
+        const PreBuild b = pre_build((uint32_t)word, (int)fmt);
+        printf("resolves %ld 0x%lx %d %d %d %d %d %d %d\n", fmt, word, b.fmt, b.w, b.ch, (int)b.probe, b.write, b.byte_path,
+               b.nt_store);
+    }
+    printf("prebuilds ok\n");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) {
+        if (argv[1] == std::string("builds")) return list_builds(argc, argv);
+        if (argv[1] == std::string("prebuilds")) return list_pre_builds(argc, argv);
+        printf("usage: %s [builds | prebuilds [FMT:WORD ...]]\n", argv[0]);
+        return 2;
     }
     // the accept masks, bit for bit the literals api.cpp held
     CHECK(kCsumModeAccept == (0x07ff7fffu | 0x11u), "0x%x", kCsumModeAccept);

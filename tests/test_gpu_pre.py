@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from prevec import java_dirty_flags, nat4_of, pre_images
 
 pytestmark = pytest.mark.gpu
 
@@ -39,43 +40,6 @@ def dev(a):
     faults hit; round 6 restores it here (DESIGN_HISTORY.md "Round 6: the intermittent fault")."""
     import torch
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def pre_images(arena, desc, rw):
-    """The vswitch's pre-images (old values of the fields each entry rewrites), recorded from the
-    frames before the setters run."""
-    from vproxy_amd import vswitch as S
-    pre = np.zeros(len(desc), O.NAT_DTYPE)
-    for i, d in enumerate(desc):
-        pre[i] = S.record_pre_image(arena, int(d["l3_off"]), int(d["l3_ver"]), int(d["l4_off"]), int(d["l4_proto"]),
-                                    int(rw[i]["mask"]) & NAT_FIELDS)
-    return pre
-
-
-def nat4_of(rw48):
-    r4 = np.zeros(len(rw48), O.NAT4_DTYPE)
-    r4["src"], r4["dst"] = rw48["src"][:, :4], rw48["dst"][:, :4]
-    r4["sport"], r4["dport"], r4["mask"] = rw48["sport"], rw48["dport"], rw48["mask"]
-    return r4
-
-
-def java_dirty_flags(desc, rw):
-    """F_IP / F_L4 as Java's setters leave a packet (checksumSkipped): IPv4 addresses and the TTL
-    dirty the header (Ipv4Packet.java:401-458); addresses dirty the L4 sum through the pseudo header
-    of TCP / UDP, and of ICMP / ICMPv6 under IPv6 (pseudoHeaderChanges, Ipv4Packet.java:236-240,
-    Ipv6Packet.java:238-242); ports dirty TCP / UDP; an L4 packet without its checksum field in the
-    segment is never dirty.  The egress defers exactly these (SwitchUtils.checksumFlagsFor)."""
-    v4 = desc["l3_ver"] == 4
-    proto = desc["l4_proto"].astype(int)
-    fld = np.array([O.L4_FIELD.get(int(p), -1) for p in proto])
-    l4sum = (fld >= 0) & ~(v4 & (proto == 58)) & \
-        (desc["l3_len"].astype(int) - desc["l4_off"].astype(int) >= fld + 2)
-    m = rw["mask"].astype(int)
-    tcpudp = (proto == 6) | (proto == 17)
-    addr_dirty = l4sum & (tcpudp | (~v4 & ((proto == 1) | (proto == 58))))
-    ip = v4 & ((m & (O.NAT_SRC | O.NAT_DST | O.NAT_SET_TTL | O.NAT_DEC_TTL)) != 0)
-    l4 = (((m & (O.NAT_SRC | O.NAT_DST)) != 0) & addr_dirty) | (l4sum & tcpudp & ((m & (O.NAT_SPORT | O.NAT_DPORT)) != 0))
-    return (np.where(ip, O.F_IP, 0) | np.where(l4, O.F_L4, 0)).astype(np.uint8)
 
 
 def assert_frames(got, want, desc, what="", whole=True):

@@ -156,6 +156,48 @@ def test_nat_build_table_is_the_header_list(launch_modes_exe):
     assert r.returncode == 0 and got == keys
 
 
+def test_pre_build_table_is_the_header_list(launch_modes_exe):
+    """tests/prebuilds.py names every k_pre build of launch_modes.h once (pre_exists over the
+    dispatcher's candidates, the two probes included), and each of its mode words resolves
+    (pre_build) to the build it stands next to with exactly the run-time switches asked for: 8
+    builds today, 6 / 2 by format.  A build added to the header without a word in the table -- so
+    without a run against the oracle in tests/test_gpu_pre_builds.py -- fails here.  The host
+    program runs under ASan / UBSan."""
+    import prebuilds as PB
+    runs = [(b, sw) for b in PB.BUILDS for sw in ((),) + tuple((s,) for s in PB.SWITCHES) + (tuple(PB.SWITCHES),)]
+    args = [f"{b.fmt}:{b.word(switches=sw):#x}" for b, sw in runs]
+    r = subprocess.run([launch_modes_exe, "prebuilds"] + args, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "prebuilds ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    exists, resolves = [], []
+    for line in r.stdout.splitlines():
+        f = line.split()
+        if f[0] == "exists":
+            exists.append(tuple(int(x) for x in f[1:]))
+        elif f[0] == "resolves":
+            resolves.append((int(f[1]), int(f[2], 16), tuple(int(x) for x in f[3:])))
+    assert len(exists) == len(set(exists)), "the header's list names a build twice"
+    assert len(resolves) == len(runs)
+    for (b, sw), (fmt, w, got) in zip(runs, resolves):
+        on = tuple(int(s in sw) for s in ("write", "byte_path", "nt_store"))
+        assert (fmt, w) == (b.fmt, b.word(switches=sw)) and got == b.key + on, (b.id, sw, hex(w), got)
+    keys = [b.key for b in PB.BUILDS]
+    assert len(set(keys)) == len(keys), "the table names a build twice"
+    assert len({b.id for b in PB.BUILDS}) == len(keys)
+    assert set(keys) == set(exists), (sorted(set(exists) - set(keys)), sorted(set(keys) - set(exists)))
+    by_fmt = {f: sum(1 for k in exists if k[0] == f) for f in (0, 1)}
+    assert by_fmt == PB.COUNT_BY_FMT and len(exists) == 8, by_fmt
+    assert sorted(PB.LIVE + PB.PROBES) == sorted(PB.BUILDS) and len(PB.PROBES) == 2
+    assert set(sw for run in PB.RUNS for sw in run) == set(PB.SWITCHES)
+    # the second-trip test's builds are in the table
+    for fmt, w in PB.SECOND_TRIP:
+        assert PB.Build(fmt, w, 6, False) in PB.BUILDS
+    # the grid field changes the grid alone
+    r = subprocess.run([launch_modes_exe, "prebuilds"] + [f"{b.fmt}:{b.word(wgs_per_cu=1):#x}" for b in PB.BUILDS],
+                       capture_output=True, text=True, timeout=120)
+    got = [tuple(int(x) for x in l.split()[3:7]) for l in r.stdout.splitlines() if l.startswith("resolves")]
+    assert r.returncode == 0 and got == keys
+
+
 def test_launch_modes_under_sanitizers(launch_modes_run):
     """The mode-word decoders (vproxy_amd/csrc/launch_modes.h: accept masks, csum_tune, nat_build,
     nat_probe_build, pre_build) equal a transcription of the launch ladders they replaced on every

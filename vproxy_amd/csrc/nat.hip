@@ -734,8 +734,15 @@ __global__ __launch_bounds__(256) void k_pre(uint8_t* __restrict__ arena, uint64
                 const int r0 = (int)((uintptr_t)l3 & 15);
                 PreSums s = {0u, 0u, false, false};
                 if (PROBE) {
-                    if (do_ip) s.ipc = ld16(w + r0 + 10);
-                    if (do_l4) s.l4c = ld16(w + r0 + l4o + fld);
+                    // a packet without a window (past it, or byte_path) has zeros in its slot: its
+                    // stored sums come from the frame, as the flush's byte path reads them
+                    if (wend[i]) {
+                        if (do_ip) s.ipc = ld16(w + r0 + 10);
+                        if (do_l4) s.l4c = ld16(w + r0 + l4o + fld);
+                    } else {
+                        if (do_ip) s.ipc = ld16(l3 + 10);
+                        if (do_l4) s.l4c = ld16(l3 + l4o + fld);
+                    }
                 } else {
                     s = wend[i] ? pre_sums(w + r0, ver, proto, len, l4o, do_ip, do_l4, rr[i])
                                 : pre_sums(l3, ver, proto, len, l4o, do_ip, do_l4, rr[i]);
