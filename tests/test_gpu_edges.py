@@ -17,6 +17,7 @@ k_csum team variants, variant 12 (one wave per packet, predicated loads), the ho
 import numpy as np
 import pytest
 
+import csumbuilds as CB
 import edgevec as E
 from oracle import oracle as O
 
@@ -70,7 +71,7 @@ def _assert_pins(packets, out):
             assert int(o) & 0xFFFF == p["want_ip"], p["kind"]
 
 
-TEAMS = [0, 2, 3, 4, 6, 7, 9, 10, 11, 12, 40, 45, 46, 47, 50, 62, 66, 70, 74]
+TEAMS = CB.IDS   # every compute variant id launch_csum accepts (tests/csumbuilds.py)
 
 
 @pytest.mark.parametrize("pad", [0, 1, 14])

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import csumbuilds as CB
 from oracle import oracle as O
 from pcaputil import l3_offset, read_pcap
 
@@ -72,7 +73,7 @@ def pack(frames, infos, stride=None, pad=0):
 
 
 @pytest.mark.parametrize("pad", [0, 1, 2, 3, 14, 15, 398])
-@pytest.mark.parametrize("team", [0, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 40, 41, 43, 45, 46, 47, 48, 49, 50, 54, 58, 62, 66, 70, 74])
+@pytest.mark.parametrize("team", CB.IDS)   # every compute variant id launch_csum accepts (tests/csumbuilds.py)
 def test_kats_on_gpu(V, orc, pad, team):
     kats, frames, infos = kat_batch()
     arena, desc = pack(frames, infos, pad=pad)

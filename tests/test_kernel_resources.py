@@ -77,6 +77,61 @@ def test_k2_default_builds_budgets():
     assert all(v["group_segment_fixed_size"] <= 26624 + 64 for v in staged_compute.values())
 
 
+def template_args(mangled: str, kernel: str):
+    """The integer / bool template arguments of `kernel<...>` in an Itanium-mangled name
+    (Li8E -> 8, Lin9E -> -9, Lb1E -> True), or None when the name is another kernel's."""
+    m = re.search(rf"\d+{kernel}I((?:L[ib]n?\d+E)+)E", mangled)
+    if not m:
+        return None
+    return tuple(bool(int(v)) if t == "b" else (-int(v[1:]) if v[0] == "n" else int(v))
+                 for t, v in re.findall(r"L([ib])(n?\d+)E", m.group(1)))
+
+
+def compiled_csum_builds():
+    ks = kernels("kernels.hip.o")
+    d = {a for a in (template_args(k, "k_csum_d") for k in ks) if a is not None}
+    t = {a for a in (template_args(k, "k_csum") for k in ks) if a is not None}
+    return d, t
+
+
+def test_template_args_decoder():
+    assert template_args("_ZN6vpcsum8k_csum_dILi8ELi6ELi2ELi2ELb0ELb1ELi1ELi0ELin9ELb1ELb0ELb0ELb0ELb0EEEvPKhm", "k_csum_d") == \
+        (8, 6, 2, 2, False, True, 1, 0, -9, True, False, False, False, False)
+    assert template_args("_ZN6vpcsum6k_csumILi64ELi4ELb1ELb0ELb1EEEvPKhm", "k_csum") == (64, 4, True, False, True)
+    assert template_args("_ZN6vpcsum6k_csumILi64ELi4ELb1ELb0ELb1EEEvPKhm", "k_csum_d") is None
+    assert template_args("_ZN6vpcsum8k_csum_dILi8ELi6ELi2ELi2ELb0ELb1ELi1ELi0ELin9ELb1ELb0ELb0ELb0ELb0EEEvPKhm", "k_csum") is None
+    assert template_args("_ZN6vpcsum14k_csum_serviceEPNS_10SvcMailboxEPjj", "k_csum") is None
+
+
+def test_csum_build_table_is_the_code_object():
+    """tests/csumbuilds.py against kernels.hip.o: the k_csum_d and k_csum kernels compiled for gfx950
+    are the table's distinct builds x VERIFY x NT, no more and no fewer -- a build added to
+    launch_csum's switch without a row (or a row whose build the switch lost) fails here."""
+    import csumbuilds as CB
+    got_d, got_t = compiled_csum_builds()
+    want_d, want_t = CB.kernel_set()
+    assert got_d == want_d, {"compiled, no row": sorted(got_d - want_d), "row, not compiled": sorted(want_d - got_d)}
+    assert got_t == want_t, {"compiled, no row": sorted(got_t - want_t), "row, not compiled": sorted(want_t - got_t)}
+    assert len(want_d) == 4 * len(CB.K2_BUILDS) == 80 and len(want_t) == 4 * len(CB.team_builds())
+
+
+def test_csum_build_table_words():
+    """The table's mode words: put together from launch_modes.h's named fields they equal
+    vpcsum._tune_bits, every id round-trips through the variant fields, and the ids are launch_csum's
+    switch as it stands (tests/test_gpu_csum_builds.py::test_id_sweep holds them to the library)."""
+    import csumbuilds as CB
+    from vproxy_amd import vpcsum
+    assert CB.IDS == [0, *range(2, 13), 40, 41, 43, 45, 46, 47, 48, 49, 50, 54, 58, 62, 66, 70, 72, 74, 76, 78, 79, 84]
+    for r in CB.ID_ROWS:
+        for plain in (False, True):
+            for no_adapt in (False, True):
+                for wgs in (0, 1, 12, 255):
+                    w = r.word(plain, no_adapt, wgs)
+                    assert w == vpcsum._tune_bits(r.id, plain, wgs, no_adapt), r.label
+                    assert ((w >> 8) & 0x1F) | (((w >> 24) & 7) << 5) == r.id and not w & 0x11   # VERIFY / WRITE free
+    assert CB.word(255, True, True, 255) == 0x07FF7F00
+
+
 def test_no_scratch_in_default_kernels():
     ks = {**kernels("kernels.hip.o"), **kernels("nat.hip.o")}
     # the NAT kernels at their default occupancy (k_natq ... WPE 1), the byte kernel, the lane
