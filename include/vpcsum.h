@@ -389,6 +389,43 @@ int vpcsum_flow_lookup_async(vpcsum_flowtab_t* tab, const vpcsum_tuple_t* d_tupl
  * Synchronises `stream`. *n_out > cap: nothing cleared, call again with room. */
 int vpcsum_flowtab_collect(vpcsum_flowtab_t* tab, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream);
 
+/* A flow's Fastpath (additive, the ABI version stays 4): what Switch.sendPacket records on the
+ * connection entry from the first packet of a flow that leaves (Fastpath.java:11-22,
+ * Switch.java:660-672) -- the Ethernet addresses the frame left with and where it went --, so that
+ * later HIT frames of the flow need no route and no MAC lookup on the host.  port is the caller's
+ * name for Fastpath.output (and the vrf, if it wants to encode one); port 0 means "no Fastpath":
+ * zeroed slots and every flow vpcsum_flowtab_update inserts have none.
+ * vpcsum_flowtab_update and the Fastpath: a new flow has none; a replaced key keeps its flow id and
+ * its Fastpath; an erased flow's Fastpath goes with it, and a flow that later takes the slot starts
+ * with none; the backward shift of an erase moves the Fastpath with its flow. */
+typedef struct vpcsum_fastpath {
+    uint8_t  dst[6];      /* Fastpath.remote: frame bytes [0,6), wire order                          */
+    uint8_t  src[6];      /* Fastpath.local: frame bytes [6,12)                                      */
+    uint32_t port;        /* 0 = no Fastpath                                                         */
+} vpcsum_fastpath_t;      /* 16 bytes */
+/* Set the Fastpath of each key h_keys[i] that is present to h_fp[i]; port 0 clears it (the stored
+ * record is then all zeros).  A key not present is not an error (the host may have erased the flow
+ * meanwhile): such keys are counted in *n_missing (may be NULL).  A malformed key (the refusals of
+ * vpcsum_flowtab_update) fails the call with nothing changed.  Ordered as vpcsum_flowtab_update: the
+ * changed slots are copied on `stream` and the call returns after those copies completed. */
+int vpcsum_flowtab_set_fastpath(vpcsum_flowtab_t* tab, const vpcsum_tuple_t* h_keys, const vpcsum_fastpath_t* h_fp,
+                                uint32_t n, uint32_t* n_missing, void* stream);
+/* vpcsum_flow_lookup_async that also writes d_fp[i] (n x 16 bytes, 4-byte aligned): the flow's
+ * Fastpath record on HIT, 16 zero bytes otherwise. */
+int vpcsum_flow_lookup_fp_async(vpcsum_flowtab_t* tab, const vpcsum_tuple_t* d_tuples, uint32_t n,
+                                vpcsum_nat_t* d_rw, uint8_t* d_verdict, vpcsum_fastpath_t* d_fp, void* stream);
+/* The L2 write of a looked-up and rewritten batch (device pointers; d_fp 4-byte aligned, d_frame_off
+ * of any alignment): frame i gets d_fp[i].dst written to its bytes [0,6), d_fp[i].src to [6,12) and
+ * d_port[i] = d_fp[i].port only when d_verdict[i] is VPCSUM_FLOW_HIT, d_status[i] has S_DONE and not
+ * S_BAD_DESC (S_MSS_ABSENT beside S_DONE does not matter) and d_fp[i].port != 0 -- exactly
+ * EthernetPacket.setDst / setSrc on a packet with its raw bytes (EthernetPacket.java:184-205):
+ * EtherType, an 802.1Q tag, lengths and padding are untouched.  Every other frame keeps its Ethernet
+ * header and gets d_port[i] = 0; so does a frame with frame_len < 14 or frame_off + frame_len >
+ * arena_len. */
+int vpcsum_l2_forward_async(uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_frame_off,
+                            const uint32_t* d_frame_len, const uint8_t* d_verdict, const uint8_t* d_status,
+                            const vpcsum_fastpath_t* d_fp, uint32_t n, uint32_t* d_port, void* stream);
+
 /* Streaming-read ceiling probe: reads `bytes` from d_buf with 16-B lanes, writes one word per
  * block into d_sink.  Used by bench.py to report a measured HBM read roof next to 8 TB/s. */
 int vpcsum_read_probe_async(const uint8_t* d_buf, uint64_t bytes, uint32_t* d_sink,
@@ -535,6 +572,17 @@ int vpcsum_ctx_nat_submit(vpcsum_ctx_t* ctx, uint8_t* h_arena, uint64_t arena_le
 int vpcsum_ctx_nat_flow_frames(vpcsum_ctx_t* ctx, vpcsum_flowtab_t* tab, uint8_t* h_arena, uint64_t arena_len,
                                const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n,
                                uint8_t* h_status, uint8_t* h_verdict, uint32_t nat_mode, uint64_t* ticket);
+/* vpcsum_ctx_nat_flow_frames that also forwards: the lookup fetches each flow's Fastpath
+ * (vpcsum_flow_lookup_fp_async) and, after the rewrite, vpcsum_l2_forward_async's rule writes the
+ * two Ethernet addresses into each HIT frame that was rewritten (S_DONE, not S_BAD_DESC) and whose
+ * flow has a Fastpath.  At vpcsum_ctx_wait h_port[i] (required when n > 0) is that flow's port --
+ * the frame is ready for that port's TX ring -- or 0: the frame's Ethernet header is as received
+ * and it takes the path it takes after vpcsum_ctx_nat_flow_frames.  Verdicts, status, rewritten
+ * bytes, marks, refusals and the launch whatever the batch size are vpcsum_ctx_nat_flow_frames'. */
+int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* ctx, vpcsum_flowtab_t* tab, uint8_t* h_arena, uint64_t arena_len,
+                                       const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n,
+                                       uint8_t* h_status, uint8_t* h_verdict, uint32_t* h_port, uint32_t nat_mode,
+                                       uint64_t* ticket);
 /* The egress flush of a batch holding NAT'd frames: vpcsum_ctx_submit where
  * descriptors with VPCSUM_F_PRE take their L4 sum from h_pre[i] (pre_fmt as vpcsum_pre_async;
  * entries of other descriptors are ignored) and the others are summed in full, in one submission.
@@ -690,6 +738,16 @@ int Java_io_vproxy_vpcsum_VPCsum_flowtabClose(PNIEnv_vpcsum_void* env, int64_t t
 int Java_io_vproxy_vpcsum_VPCsum_natFlowFrames(PNIEnv_vpcsum_long* env, int64_t ctx, int64_t tab, void* arena,
                                                int64_t arenaLen, void* frameOff, void* frameLen, int32_t n, void* status,
                                                void* verdict, int32_t natMode);
+/* VPCsum.flowtabSetFastpath(long tab, MemorySegment keys, MemorySegment fp, int n) -> int missing:
+ * 40-B vpcsum_tuple_t keys and their 16-B vpcsum_fastpath_t records (vpcsum_flowtab_set_fastpath,
+ * stream NULL, ordered as flowtabUpdate); the keys that were not in the table are counted */
+int Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath(PNIEnv_vpcsum_int* env, int64_t tab, void* keys, void* fp, int32_t n);
+/* VPCsum.natFlowForwardFrames(long ctx, long tab, MemorySegment arena, long arenaLen, MemorySegment frameOff,
+ *                             MemorySegment frameLen, int n, MemorySegment status, MemorySegment verdict,
+ *                             MemorySegment port, int natMode) -> long ticket (vpcsum_ctx_nat_flow_forward_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames(PNIEnv_vpcsum_long* env, int64_t ctx, int64_t tab, void* arena,
+                                                      int64_t arenaLen, void* frameOff, void* frameLen, int32_t n,
+                                                      void* status, void* verdict, void* port, int32_t natMode);
 /* VPCsum.setService(long ctx, int idleUs) */
 int Java_io_vproxy_vpcsum_VPCsum_setService(PNIEnv_vpcsum_void* env, int64_t ctx, int32_t idleUs);
 /* VPCsum.waitFor(long ctx, long ticket) */

@@ -382,6 +382,22 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * {@link #natFlow} that also forwards (L4Output's fastpath branch, L4Output.java:38-77, without
+     * the host): a FLOW_HIT frame that was rewritten and whose flow has a Fastpath
+     * (VPCsum.flowtabSetFastpath, from what Switch.sendPacket recorded) gets the Fastpath's Ethernet
+     * addresses written in place.  Fills {@code portOut} (u32 per frame): not 0 -- queue the frame on
+     * that port's TX ring as it lies; 0 -- the Ethernet header is as received, go on as after natFlow.
+     */
+    public MemorySegment natFlowForward(long tab, MemorySegment frameOff, MemorySegment frameLen, int count, boolean strictJava,
+                                        MemorySegment statusOut, MemorySegment verdictOut, MemorySegment portOut)
+        throws IOException {
+        long t = VPCsum.get().natFlowForwardFrames(env, ctx, tab, umem, umemLen, frameOff, frameLen, count, statusOut, verdictOut,
+            portOut, strictJava ? VPCsum.NAT_STRICT_JAVA : VPCsum.NAT_RFC1624);
+        VPCsum.get().waitFor(env, ctx, t);
+        return portOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

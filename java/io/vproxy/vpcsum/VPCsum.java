@@ -481,6 +481,60 @@ public class VPCsum {
         return ENV.returnLong();
     }
 
+    private static final MethodHandle flowtabSetFastpathMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath", long.class /* tab */, MemorySegment.class /* keys */,
+        MemorySegment.class /* fp */, int.class /* n */);
+
+    /** Sets the Fastpath of {@code n} flows: {@code keys} 40-byte vpcsum_tuple_t each, {@code fp}
+     * 16-byte vpcsum_fastpath_t each -- dst[6] (Fastpath.remote), src[6] (Fastpath.local), u32 port
+     * (the caller's name for Fastpath.output; 0 clears the record).  What Switch.sendPacket records
+     * on the connection entry, once the first packet of that direction has left by the host's path.
+     * Returns how many keys were not in the table (erased meanwhile: not an error); a malformed key
+     * throws and changes nothing.  Ordered like {@link #flowtabUpdate}. */
+    public int flowtabSetFastpath(PNIEnv ENV, long tab, MemorySegment keys, MemorySegment fp, int n) throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) flowtabSetFastpathMH.invokeExact(ENV.MEMORY, tab, keys, fp, n);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnInt();
+    }
+
+    private static final MethodHandle natFlowForwardFramesMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames", long.class /* ctx */, long.class /* tab */, MemorySegment.class /* arena */,
+        long.class /* arenaLen */, MemorySegment.class /* frameOff */, MemorySegment.class /* frameLen */, int.class /* n */,
+        MemorySegment.class /* status */, MemorySegment.class /* verdict */, MemorySegment.class /* port */, int.class /* natMode */);
+
+    /** {@link #natFlowFrames} that also forwards: a FLOW_HIT frame that was rewritten (S_DONE, not
+     * S_BAD_DESC) and whose flow has a Fastpath gets the record's two Ethernet addresses written
+     * (EthernetPacket.setDst / setSrc on the raw bytes: nothing else of the frame changes) and
+     * port[i] (u32 each) = the record's port: the frame is ready for that port's TX ring.
+     * port[i] == 0: the frame's Ethernet header is as received and it takes the path it takes after
+     * {@link #natFlowFrames}. */
+    public long natFlowForwardFrames(PNIEnv ENV, long ctx, long tab, MemorySegment arena, long arenaLen, MemorySegment frameOff,
+                                     MemorySegment frameLen, int n, MemorySegment status, MemorySegment verdict,
+                                     MemorySegment port, int natMode) throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) natFlowForwardFramesMH.invokeExact(ENV.MEMORY, ctx, tab, arena, arenaLen, frameOff, frameLen, n, status, verdict,
+                port, natMode);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
     private static final MethodHandle setServiceMH =PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
         "Java_io_vproxy_vpcsum_VPCsum_setService", long.class /* ctx */, int.class /* idleUs */);
 

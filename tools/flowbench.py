@@ -4,8 +4,12 @@ frames), timed with events over 100 launches after warm-up, legs in alternating 
   b  vpcsum_flow_lookup_async alone: 64 K, 256 K and 1 M flows, 100 % hits and 50 % misses
   c  vpcsum_nat_async with host-prepared 48-B entries (the reference figure: the code before the table)
   d  a + b + c on one stream (1 M flows: every frame's flow is in the table)
+  e  d with the Fastpath: parse, vpcsum_flow_lookup_fp_async, rewrite, vpcsum_l2_forward_async (every
+     flow carries a Fastpath, so every frame gets its Ethernet addresses written and a port)
+  f  vpcsum_l2_forward_async alone, on the verdicts, status bytes and records e left
 The flows are the frames' own tuples; every entry rewrites both addresses and both ports to the values
-the frame already carries, so the frames -- and their tuples -- stay the same launch after launch.
+the frame already carries, and every Fastpath carries the Ethernet addresses all frames have, so the
+frames -- and their tuples -- stay the same launch after launch.
 Prints one JSON line.  usage: flowbench.py [frames] [--launches N]"""
 import json
 import os
@@ -28,6 +32,8 @@ d = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
 V.synth(arena, n, stride, l2, V.SYNTH_C5, 0x20241020, 0, d)
 fr = arena.view(n, stride)
 fr[:, 12], fr[:, 13] = 0x08, 0x00                # EtherType IPv4
+MACS = bytes.fromhex("02aa00000001" "02bb00000002")  # one pair of Ethernet addresses on every frame: e rewrites the same
+fr[:, :12] = torch.tensor(list(MACS), dtype=torch.uint8, device="cuda")
 fr[:, l2 + 20 + 13] = 0x10                       # TCP: ACK alone (no PUNT); UDP: a payload byte
 V.compute(arena, d, n, None, None, V.MODE_WRITE)  # valid stored sums: RFC 1624's premise
 foff = (torch.arange(n, dtype=torch.int64, device="cuda") * stride).contiguous()
@@ -110,6 +116,27 @@ def chain():
 
 
 legs["d_chain_parse_lookup_nat"] = chain
+# e: every flow of the big table gets a Fastpath (the frames' own addresses, port = cookie + 1)
+fkeys = keys[distinct[:max(FLOWS)]]
+frec = np.zeros(len(fkeys), V.FASTPATH_DTYPE)
+frec["dst"], frec["src"] = np.frombuffer(MACS[:6], np.uint8), np.frombuffer(MACS[6:], np.uint8)
+frec["port"] = (distinct[:max(FLOWS)] + 1).astype(np.uint32)
+assert big.set_fastpath(fkeys, frec) == 0
+fp = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+port = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+
+def chain_fp():
+    V.parse_ether(arena, foff, flen, n, desc, None, tuples=tu)
+    big.lookup(tu, n, rw, vd, fastpath=fp)
+    V.nat(arena, desc, rw, n, st, V.NAT_RFC1624)
+    V.l2_forward(arena, foff, flen, vd, st, fp, n, port)
+
+
+chain_fp()   # f's inputs
+torch.cuda.synchronize()
+legs["e_chain_fastpath_l2"] = chain_fp
+legs["f_l2_forward_alone"] = lambda: V.l2_forward(arena, foff, flen, vd, st, fp, n, port)
 before = arena[: 64 * stride].clone()
 us = {k: [] for k in legs}
 for _ in range(rounds):
@@ -117,6 +144,8 @@ for _ in range(rounds):
         us[k].append(round(timed(fn), 2))
 assert int((st & V.S_BAD_DESC).sum().item()) == 0
 assert torch.equal(arena[: 64 * stride], before), "the identity rewrite left the frames as they were"
+if res["chain_hit_fraction"] == 1.0:
+    assert int((port == 0).sum().item()) == 0, "every frame of e has a port"
 for k, v in us.items():
     med = sorted(v)[len(v) // 2]
     res[k] = {"us_rounds": v, "us_median": med, "Gpps": round(n / med / 1e3, 3)}
@@ -130,5 +159,7 @@ for F in FLOWS:
     res["tables"][f"{F >> 10}K"].update(load=round(a, 3), bytes_per_hit=round(40 + 128 * ph + 50, 1),
                                         bytes_per_miss=round(40 + 128 * pm + 49, 1), table_MiB=info[F]["slots"] * 128 >> 20)
 res["pcie_bound_Gpps_16B_entries"] = 4.0
+res["e_over_d"] = round(res["e_chain_fastpath_l2"]["us_median"] / res["d_chain_parse_lookup_nat"]["us_median"], 4)
+res["e_minus_d_us"] = round(res["e_chain_fastpath_l2"]["us_median"] - res["d_chain_parse_lookup_nat"]["us_median"], 2)
 res["chain_vs_pcie_bound"] = round(res["d_chain_parse_lookup_nat"]["Gpps"] / 4.0, 2)
 print(json.dumps(res))

@@ -142,6 +142,7 @@ struct Batch {
     vpcsum_tuple_t* user_tuples = nullptr;
     vpcsum_hsum_t* user_hsum = nullptr;       // verify batch with header sums: where they go
     uint8_t* user_verdict = nullptr;          // flow batch (vpcsum_ctx_nat_flow_frames): where the verdicts go
+    uint32_t* user_port = nullptr;            // forwarding flow batch: where the output ports go
 };
 
 // Per-slot staging of one in-flight batch of a context.
@@ -162,6 +163,8 @@ struct Slot {
     Mapped<vpcsum_hsum_t> h_hs;        // ingress header sums of a verify batch: with the first such batch
     vpcsum_tuple_t* d_tu = nullptr;    // a flow batch's tuples (parse -> lookup, device only) and its verdicts:
     Mapped<uint8_t> h_verdict;         // with the context's first flow batch
+    vpcsum_fastpath_t* d_fp = nullptr; // a forwarding flow batch's Fastpath records (lookup -> L2 write, device only)
+    Mapped<uint32_t> h_port;           // and its output ports: with the context's first such batch
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool busy = false;                 // `batch` is in flight
@@ -689,6 +692,8 @@ static void slot_free(Slot& s) {
     s.h_hs.free();
     if (s.d_tu) (void)hipFree(s.d_tu);
     s.h_verdict.free();
+    if (s.d_fp) (void)hipFree(s.d_fp);
+    s.h_port.free();
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = Slot();
@@ -970,6 +975,7 @@ static int slot_finish(vpcsum_ctx* c, Slot& s) {
     const uint8_t* aux = c->svc.h_pre.p;
     if (b.user_status) memcpy(b.user_status, res_status, b.n);
     if (b.user_verdict) memcpy(b.user_verdict, s.h_verdict.p, b.n);
+    if (b.user_port) memcpy(b.user_port, s.h_port.p, (size_t)b.n * 4);
     switch (b.kind) {
     case BatchKind::Nat:
         // a staged batch's rewritten headers (L3 header through the L4 checksum field; the TCP
@@ -1588,10 +1594,38 @@ static void sort_unique(std::vector<uint32_t>& v) {
 
 // The lookup of a batch on the table's device; caller holds f->mu (max_probe and the launch are one
 // step against a concurrent update).
+// d_fp != NULL: the lookup that also writes the flows' Fastpath records.
 static int flow_lookup_locked(vpcsum_flowtab* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
-                              uint8_t* d_verdict, hipStream_t s) {
-    VPC_CHECK(launch_flow_lookup(f->d_slots, f->t->mask(), f->t->max_probe(), f->d_touched, d_tuples, n, d_rw, d_verdict, s),
+                              uint8_t* d_verdict, vpcsum_fastpath_t* d_fp, hipStream_t s) {
+    VPC_CHECK(launch_flow_lookup(f->d_slots, f->t->mask(), f->t->max_probe(), f->d_touched, d_tuples, n, d_rw, d_verdict,
+                                 d_fp, s),
               "flow lookup launch");
+    return 0;
+}
+
+// The mirror's changed slots to the device on stream s, and the wait for them (so that the mirror is
+// not written again while a copy reads it); caller holds f->mu on f's device.  `freed`: the flow ids
+// an update erased, whose marks go with them (an id may be handed to another flow).
+static int flowtab_push(vpcsum_flowtab* f, FlowDirty& dirty, std::vector<uint32_t>& freed, hipStream_t s, const char* what) {
+    sort_unique(dirty.idx);
+    sort_unique(freed);
+    // the whole table in one copy instead of its runs: a bulk load (an eighth of the slots or
+    // more changed), more slots written than `dirty` had room for, or an earlier copy that failed
+    const bool whole = dirty.all || f->resync || dirty.idx.size() >= f->t->slots() / 8u;
+    f->resync = true;   // until the copies below are queued
+    int rc = for_runs(freed, [&](uint32_t a, uint32_t b) {
+        const hipError_t e = hipMemsetAsync(f->d_touched + a, 0, b - a, s);
+        return e == hipSuccess ? 0 : fail("%s: clearing marks: %s (%d)", what, hipGetErrorString(e), (int)e);
+    });
+    auto copy_slots = [&](uint32_t a, uint32_t b) {
+        const hipError_t e = hipMemcpyAsync(f->d_slots + a, f->h_slots + a, (size_t)(b - a) * sizeof(FlowSlot), hipMemcpyHostToDevice, s);
+        return e == hipSuccess ? 0 : fail("%s: H2D slots: %s (%d)", what, hipGetErrorString(e), (int)e);
+    };
+    if (rc == 0) rc = whole ? copy_slots(0, f->t->slots()) : for_runs(dirty.idx, copy_slots);
+    const hipError_t e = hipStreamSynchronize(s);   // also after a failed copy: none reads the mirror after the return
+    if (rc != 0) return -1;   // the mirror is ahead of the device: the next update copies everything (resync)
+    if (e != hipSuccess) return fail("%s: hipStreamSynchronize: %s (%d)", what, hipGetErrorString(e), (int)e);
+    f->resync = false;
     return 0;
 }
 
@@ -1657,29 +1691,7 @@ int vpcsum_flowtab_update(vpcsum_flowtab_t* f, const vpcsum_tuple_t* h_del, uint
             if (id >= 0) freed.push_back((uint32_t)id);
         }
         for (uint32_t i = 0; i < n_add; ++i) (void)f->t->insert(h_add[i], &dirty);
-        sort_unique(dirty.idx);
-        sort_unique(freed);
-        // the whole table in one copy instead of its runs: a bulk load (an eighth of the slots or
-        // more changed), more slots written than `dirty` had room for, or an earlier copy that failed
-        const bool whole = dirty.all || f->resync || dirty.idx.size() >= f->t->slots() / 8u;
-        f->resync = true;   // until the copies below are queued
-        hipStream_t s = (hipStream_t)stream;
-        // an erased flow's mark goes with it: the id may be handed to another flow
-        int rc = for_runs(freed, [&](uint32_t a, uint32_t b) {
-            VPC_CHECK(hipMemsetAsync(f->d_touched + a, 0, b - a, s), "vpcsum_flowtab_update: clearing marks");
-            return 0;
-        });
-        auto copy_slots = [&](uint32_t a, uint32_t b) {
-            VPC_CHECK(hipMemcpyAsync(f->d_slots + a, f->h_slots + a, (size_t)(b - a) * sizeof(FlowSlot), hipMemcpyHostToDevice, s),
-                      "vpcsum_flowtab_update: H2D slots");
-            return 0;
-        };
-        if (rc == 0) rc = whole ? copy_slots(0, f->t->slots()) : for_runs(dirty.idx, copy_slots);
-        const hipError_t e = hipStreamSynchronize(s);   // also after a failed copy: none reads the mirror after the return
-        if (rc != 0) return -1;   // the mirror is ahead of the device: the next update copies everything (resync)
-        VPC_CHECK(e, "vpcsum_flowtab_update: hipStreamSynchronize");
-        f->resync = false;
-        return 0;
+        return flowtab_push(f, dirty, freed, (hipStream_t)stream, "vpcsum_flowtab_update");
     } VPC_CATCH("vpcsum_flowtab_update")
 }
 
@@ -1712,8 +1724,61 @@ int vpcsum_flow_lookup_async(vpcsum_flowtab_t* f, const vpcsum_tuple_t* d_tuples
         if (n > (1u << 28)) return fail("vpcsum_flow_lookup_async: %u packets > 2^28", n);
         std::lock_guard<std::mutex> lk(f->mu);
         VPC_ON_DEVICE(f->device);
-        return flow_lookup_locked(f, d_tuples, n, d_rw, d_verdict, (hipStream_t)stream);
+        return flow_lookup_locked(f, d_tuples, n, d_rw, d_verdict, nullptr, (hipStream_t)stream);
     } VPC_CATCH("vpcsum_flow_lookup_async")
+}
+
+int vpcsum_flowtab_set_fastpath(vpcsum_flowtab_t* f, const vpcsum_tuple_t* h_keys, const vpcsum_fastpath_t* h_fp, uint32_t n,
+                                uint32_t* n_missing, void* stream) {
+    try {
+        if (!f) return fail("vpcsum_flowtab_set_fastpath: NULL table");
+        if (n && (!h_keys || !h_fp)) return fail("vpcsum_flowtab_set_fastpath: NULL keys or Fastpath records");
+        std::lock_guard<std::mutex> lk(f->mu);
+        VPC_ON_DEVICE(f->device);
+        // every key checked, and the bookkeeping's room made, before the table changes
+        for (uint32_t i = 0; i < n; ++i)
+            if (const char* r = flow_key_refusal(h_keys[i])) return fail("vpcsum_flowtab_set_fastpath: key %u: %s", i, r);
+        FlowDirty dirty((size_t)n + 16);
+        std::vector<uint32_t> none;
+        uint32_t missing = 0;
+        for (uint32_t i = 0; i < n; ++i) missing += f->t->set_fastpath(h_keys[i], h_fp[i], &dirty) == 0 ? 1u : 0u;
+        if (n_missing) *n_missing = missing;
+        return flowtab_push(f, dirty, none, (hipStream_t)stream, "vpcsum_flowtab_set_fastpath");
+    } VPC_CATCH("vpcsum_flowtab_set_fastpath")
+}
+
+int vpcsum_flow_lookup_fp_async(vpcsum_flowtab_t* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
+                                uint8_t* d_verdict, vpcsum_fastpath_t* d_fp, void* stream) {
+    try {
+        if (!f) return fail("vpcsum_flow_lookup_fp_async: NULL table");
+        if (n == 0) return 0;
+        if (!d_tuples || !d_rw || !d_verdict || !d_fp)
+            return fail("vpcsum_flow_lookup_fp_async: NULL tuples, entries, verdicts or Fastpath records");
+        if (((uintptr_t)d_tuples | (uintptr_t)d_rw | (uintptr_t)d_fp) & 3)
+            return fail("vpcsum_flow_lookup_fp_async: tuples / entries / Fastpath records not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_flow_lookup_fp_async: %u packets > 2^28", n);
+        std::lock_guard<std::mutex> lk(f->mu);
+        VPC_ON_DEVICE(f->device);
+        return flow_lookup_locked(f, d_tuples, n, d_rw, d_verdict, d_fp, (hipStream_t)stream);
+    } VPC_CATCH("vpcsum_flow_lookup_fp_async")
+}
+
+int vpcsum_l2_forward_async(uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_frame_off, const uint32_t* d_frame_len,
+                            const uint8_t* d_verdict, const uint8_t* d_status, const vpcsum_fastpath_t* d_fp, uint32_t n,
+                            uint32_t* d_port, void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_arena || !d_frame_off || !d_frame_len || !d_verdict || !d_status || !d_fp || !d_port)
+            return fail("vpcsum_l2_forward_async: NULL argument");
+        if ((uintptr_t)d_frame_off & 7) return fail("vpcsum_l2_forward_async: frame offsets not 8-byte aligned");
+        if (((uintptr_t)d_frame_len | (uintptr_t)d_fp | (uintptr_t)d_port) & 3)
+            return fail("vpcsum_l2_forward_async: frame lengths / Fastpath records / ports not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_l2_forward_async: %u frames > 2^28", n);
+        VPC_CHECK(launch_l2_forward(d_arena, arena_len, d_frame_off, d_frame_len, d_verdict, d_status, d_fp, n, d_port,
+                                    (hipStream_t)stream),
+                  "L2 forward launch");
+        return 0;
+    } VPC_CATCH("vpcsum_l2_forward_async")
 }
 
 int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream) {
@@ -1737,44 +1802,73 @@ int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t ca
     } VPC_CATCH("vpcsum_flowtab_collect")
 }
 
+// vpcsum_ctx_nat_flow_frames (h_port NULL, forward false) / vpcsum_ctx_nat_flow_forward_frames
+static int ctx_nat_flow_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uint8_t* h_arena, uint64_t arena_len,
+                               const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n, uint8_t* h_status,
+                               uint8_t* h_verdict, uint32_t* h_port, bool forward, uint32_t nat_mode, uint64_t* ticket,
+                               const char* what) {
+    if (!f) return fail("%s: NULL flow table", what);
+    if (c && f->device != c->device)
+        return fail("%s: the flow table lives on device %d, the context on device %d", what, f->device, c->device);
+    if (nat_mode & ~kNatCtxModeAccept) return fail("%s: bad nat_mode 0x%x", what, nat_mode);
+    if (n && !h_verdict) return fail("%s: NULL verdicts", what);
+    if (n && forward && !h_port) return fail("%s: NULL ports", what);
+    // the service grid has no lookup: the batch is launched whatever its size (may_svc false)
+    return frames_entry(c, what, "arena, frame table or status", h_arena, arena_len, h_frame_off, h_frame_len, h_status, n,
+                        ticket, [&](Slot& s, Batch b, uint8_t* base, bool) {
+        b.kind = BatchKind::Nat;   // zero-copy: the frames are rewritten where they lie
+        b.mode = nat_mode;
+        b.user_status = h_status;
+        b.user_verdict = h_verdict;
+        b.user_port = forward && n ? h_port : nullptr;
+        if (n) {
+            // per-packet scratch of the chain, sized from max_pkts with the context's first such
+            // batch: tuples and entries on the device, verdicts in pinned memory
+            if (slot_rw_alloc(c, s, what) != 0) return -1;
+            if (!s.d_tu) VPC_CHECK(hipMalloc((void**)&s.d_tu, (size_t)c->max_pkts * sizeof(vpcsum_tuple_t)), what);
+            if (!s.h_verdict.p) VPC_CHECK(s.h_verdict.alloc(c->max_pkts), what);
+            // a forwarding batch: Fastpath records on the device, ports in pinned memory
+            if (forward && !s.d_fp) VPC_CHECK(hipMalloc((void**)&s.d_fp, (size_t)c->max_pkts * sizeof(vpcsum_fastpath_t)), what);
+            if (forward && !s.h_port.p) VPC_CHECK(s.h_port.alloc((size_t)c->max_pkts * 4), what);
+            // parse -> tuples -> lookup -> entries -> rewrite (-> L2 write), one stream; the parse's
+            // status bytes are not needed: a refused frame's descriptor is all zeros, which the
+            // rewrite refuses (S_BAD_DESC, nothing written)
+            VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
+                                         nullptr, s.d_tu, s.stream),
+                      "parse launch");
+            {
+                std::lock_guard<std::mutex> lf(f->mu);
+                if (flow_lookup_locked(f, s.d_tu, n, s.d_rw, s.h_verdict.dev, forward ? s.d_fp : nullptr, s.stream) != 0)
+                    return -1;
+            }
+            if (nat_run(base, arena_len, s.d_desc, s.d_rw, 1, n, s.h_status.dev, nat_mode, s.stream) != 0) return -1;
+            // the rewrite's status says which HIT frames are complete: those get their flow's addresses
+            if (forward)
+                VPC_CHECK(launch_l2_forward(base, arena_len, s.h_foff.dev, s.h_flen.dev, s.h_verdict.dev, s.h_status.dev, s.d_fp,
+                                            n, s.h_port.dev, s.stream),
+                          "L2 forward launch");
+        }
+        return slot_commit(s, b, ticket);
+    }, false);
+}
+
 int vpcsum_ctx_nat_flow_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uint8_t* h_arena, uint64_t arena_len,
                                const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n, uint8_t* h_status,
                                uint8_t* h_verdict, uint32_t nat_mode, uint64_t* ticket) {
     try {
-        const char* what = "vpcsum_ctx_nat_flow_frames";
-        if (!f) return fail("%s: NULL flow table", what);
-        if (c && f->device != c->device)
-            return fail("%s: the flow table lives on device %d, the context on device %d", what, f->device, c->device);
-        if (nat_mode & ~kNatCtxModeAccept) return fail("%s: bad nat_mode 0x%x", what, nat_mode);
-        if (n && !h_verdict) return fail("%s: NULL verdicts", what);
-        // the service grid has no lookup: the batch is launched whatever its size (may_svc false)
-        return frames_entry(c, what, "arena, frame table or status", h_arena, arena_len, h_frame_off, h_frame_len, h_status, n,
-                            ticket, [&](Slot& s, Batch b, uint8_t* base, bool) {
-            b.kind = BatchKind::Nat;   // zero-copy: the frames are rewritten where they lie
-            b.mode = nat_mode;
-            b.user_status = h_status;
-            b.user_verdict = h_verdict;
-            if (n) {
-                // per-packet scratch of the chain, sized from max_pkts with the context's first such
-                // batch: tuples and entries on the device, verdicts in pinned memory
-                if (slot_rw_alloc(c, s, what) != 0) return -1;
-                if (!s.d_tu) VPC_CHECK(hipMalloc((void**)&s.d_tu, (size_t)c->max_pkts * sizeof(vpcsum_tuple_t)), what);
-                if (!s.h_verdict.p) VPC_CHECK(s.h_verdict.alloc(c->max_pkts), what);
-                // parse -> tuples -> lookup -> entries -> rewrite, one stream; the parse's status
-                // bytes are not needed: a refused frame's descriptor is all zeros, which the rewrite
-                // refuses (S_BAD_DESC, nothing written)
-                VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
-                                             nullptr, s.d_tu, s.stream),
-                          "parse launch");
-                {
-                    std::lock_guard<std::mutex> lf(f->mu);
-                    if (flow_lookup_locked(f, s.d_tu, n, s.d_rw, s.h_verdict.dev, s.stream) != 0) return -1;
-                }
-                if (nat_run(base, arena_len, s.d_desc, s.d_rw, 1, n, s.h_status.dev, nat_mode, s.stream) != 0) return -1;
-            }
-            return slot_commit(s, b, ticket);
-        }, false);
+        return ctx_nat_flow_frames(c, f, h_arena, arena_len, h_frame_off, h_frame_len, n, h_status, h_verdict, nullptr, false,
+                                   nat_mode, ticket, "vpcsum_ctx_nat_flow_frames");
     } VPC_CATCH("vpcsum_ctx_nat_flow_frames")
+}
+
+int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uint8_t* h_arena, uint64_t arena_len,
+                                       const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n,
+                                       uint8_t* h_status, uint8_t* h_verdict, uint32_t* h_port, uint32_t nat_mode,
+                                       uint64_t* ticket) {
+    try {
+        return ctx_nat_flow_frames(c, f, h_arena, arena_len, h_frame_off, h_frame_len, n, h_status, h_verdict, h_port, true,
+                                   nat_mode, ticket, "vpcsum_ctx_nat_flow_forward_frames");
+    } VPC_CATCH("vpcsum_ctx_nat_flow_forward_frames")
 }
 
 int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint32_t copy_bytes,
@@ -2403,6 +2497,33 @@ int Java_io_vproxy_vpcsum_VPCsum_natFlowFrames(PNIEnv_vpcsum_long* env, int64_t 
         return vpcsum_ctx_nat_flow_frames((vpcsum_ctx_t*)(intptr_t)ctx, (vpcsum_flowtab_t*)(intptr_t)tab, (uint8_t*)arena,
                                           (uint64_t)arenaLen, (const uint64_t*)frameOff, (const uint32_t*)frameLen,
                                           (uint32_t)n, (uint8_t*)status, (uint8_t*)verdict, (uint32_t)natMode, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath(PNIEnv_vpcsum_int* env, int64_t tab, void* keys, void* fp, int32_t n) {
+    try {
+        if (n < 0) {
+            fail("flowtabSetFastpath: negative count");
+            return pni_throw(env, "java.lang.IllegalArgumentException");
+        }
+        uint32_t missing = 0;
+        if (vpcsum_flowtab_set_fastpath((vpcsum_flowtab_t*)(intptr_t)tab, (const vpcsum_tuple_t*)keys,
+                                        (const vpcsum_fastpath_t*)fp, (uint32_t)n, &missing, nullptr) != 0)
+            return pni_throw(env, "java.io.IOException");
+        env->return_ = (int32_t)missing;
+        return 0;
+    } VPC_CATCH_PNI("Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath")
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames(PNIEnv_vpcsum_long* env, int64_t ctx, int64_t tab, void* arena,
+                                                      int64_t arenaLen, void* frameOff, void* frameLen, int32_t n,
+                                                      void* status, void* verdict, void* port, int32_t natMode) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames", n < 0 || arenaLen < 0,
+                         "natFlowForwardFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_nat_flow_forward_frames((vpcsum_ctx_t*)(intptr_t)ctx, (vpcsum_flowtab_t*)(intptr_t)tab,
+                                                  (uint8_t*)arena, (uint64_t)arenaLen, (const uint64_t*)frameOff,
+                                                  (const uint32_t*)frameLen, (uint32_t)n, (uint8_t*)status, (uint8_t*)verdict,
+                                                  (uint32_t*)port, (uint32_t)natMode, t);
     });
 }
 

@@ -1,6 +1,7 @@
-// flow.hip -- the NAT flow table's lookup kernel (vpcsum_flow_lookup_async): per packet, the tuple
-// the parse wrote is hashed, its home slot and up to max_probe more are read, and the flow's
-// vpcsum_nat_t entry -- or zeros -- is written for the rewrite kernel that runs next on the stream.
+// flow.hip -- the NAT flow table's lookup kernels (vpcsum_flow_lookup_async, _fp_async): per packet,
+// the tuple the parse wrote is hashed, its home slot and up to max_probe more are read, and the flow's
+// vpcsum_nat_t entry -- or zeros -- is written for the rewrite kernel that runs next on the stream
+// (k_flowfp: the flow's Fastpath too); and the L2 write that follows the rewrite (k_l2_forward).
 //
 // Shape: a team of 8 lanes per packet, the shape K2 uses for frames.  A slot is one 128-B line
 // (flow_table.h FlowSlot) and each lane of the team loads 16 B of it, so one load instruction
@@ -9,7 +10,8 @@
 //   lane 1  key.dst                      ... dst
 //   lane 2  ports, version, protocol | flow id | occupied
 //   lanes 3..5  the 48-B entry: on a HIT stored as it was loaded, 3 x 16 B contiguous
-//   lanes 6..7  cookie, padding: loaded (the line comes whole) and not used
+//   lane 6  cookie, padding: loaded (the line comes whole) and not used
+//   lane 7  the flow's Fastpath (vpcsum_fastpath_t): stored by k_flowfp, not used by k_flow_lookup
 // The tuple is loaded in the same layout (lanes 0..2), so the key compare is lane-local and the
 // team's verdict one ballot; the hash is the sum of per-word mixes (flow_table.h), each lane mixing
 // the words it holds, added across the team with three shuffles.
@@ -35,10 +37,13 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-__global__ __launch_bounds__(256) void k_flow_lookup(const FlowSlot* __restrict__ slots, uint32_t mask, uint32_t max_probe,
-                                                    uint8_t* __restrict__ touched,
-                                                    const vpcsum_tuple_t* __restrict__ tuples, uint32_t n,
-                                                    vpcsum_nat_t* __restrict__ rw_out, uint8_t* __restrict__ verdict_out) {
+// The lookup of one packet by its team, whole: the body of both kernels, so that the two cannot
+// drift.  FP (a constant at each call): lane 7 also stores the flow's Fastpath.
+template <bool FP>
+__device__ __forceinline__ void flow_lookup_team(const FlowSlot* __restrict__ slots, uint32_t mask, uint32_t max_probe,
+                                                 uint8_t* __restrict__ touched, const vpcsum_tuple_t* __restrict__ tuples,
+                                                 uint32_t n, vpcsum_nat_t* __restrict__ rw_out,
+                                                 uint8_t* __restrict__ verdict_out, vpcsum_fastpath_t* __restrict__ fp_out) {
     const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
     const uint32_t pkt = tid >> 3;          // one team of 8 lanes per packet
     const uint32_t l8 = threadIdx.x & 7u;   // the lane's 16-B piece of a slot
@@ -104,16 +109,123 @@ __global__ __launch_bounds__(256) void k_flow_lookup(const FlowSlot* __restrict_
         if (hit) touched[s2] = 1;   // s2: the flow id; a plain byte store of a constant, idempotent
     } else if (l8 == 0) {
         verdict_out[pkt] = hit ? (uint8_t)VPCSUM_FLOW_HIT : punt ? (uint8_t)VPCSUM_FLOW_PUNT : (uint8_t)VPCSUM_FLOW_MISS;
+    } else if (FP && l8 == 7) {
+        // the flow's Fastpath (slot bytes 112..127) as loaded, or zeros
+        u32x4a4_t o;
+        o.x = hit ? s0 : 0u; o.y = hit ? s1 : 0u; o.z = hit ? s2 : 0u; o.w = hit ? s3 : 0u;
+        *(gw_u32x4a4_t*)(fp_out + pkt) = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_flow_lookup(const FlowSlot* __restrict__ slots, uint32_t mask, uint32_t max_probe,
+                                                    uint8_t* __restrict__ touched,
+                                                    const vpcsum_tuple_t* __restrict__ tuples, uint32_t n,
+                                                    vpcsum_nat_t* __restrict__ rw_out, uint8_t* __restrict__ verdict_out) {
+    flow_lookup_team<false>(slots, mask, max_probe, touched, tuples, n, rw_out, verdict_out, nullptr);
+}
+
+// The lookup that also hands out the flow's Fastpath: lane 7 holds the slot's bytes 112..127, the
+// vpcsum_fastpath_t, and stores them as loaded on a HIT, zeros otherwise.
+__global__ __launch_bounds__(256) void k_flowfp(const FlowSlot* __restrict__ slots, uint32_t mask, uint32_t max_probe,
+                                               uint8_t* __restrict__ touched, const vpcsum_tuple_t* __restrict__ tuples,
+                                               uint32_t n, vpcsum_nat_t* __restrict__ rw_out,
+                                               uint8_t* __restrict__ verdict_out, vpcsum_fastpath_t* __restrict__ fp_out) {
+    flow_lookup_team<true>(slots, mask, max_probe, touched, tuples, n, rw_out, verdict_out, fp_out);
+}
+
+// ------------------------------------------------------------------------------------------
+// The L2 write (vpcsum_l2_forward_async): one lane per frame.  A frame's 12 address bytes start at
+// arena + frame_off, of any alignment; they are held as three little-endian dwords and leave in the
+// widest naturally aligned stores the address allows -- 3 stores at a 4-B aligned address, 4 at an
+// even one, 5 at an odd one -- each store's bytes cut from the dwords at compile-time positions
+// (one instantiation per address residue mod 4: no indexed register array, no scratch).
+// ------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(1))) uint32_t gw32_t;
+typedef __attribute__((address_space(1))) uint16_t gw16_t;
+typedef __attribute__((address_space(1))) uint8_t gw8_t;
+
+// bytes [POS, POS + 4) of the 12 (POS <= 8; a tail store uses fewer of them)
+template <int POS>
+__device__ __forceinline__ uint32_t mac_bytes(uint32_t w0, uint32_t w1, uint32_t w2) {
+    constexpr int k = POS >> 2, sh = (POS & 3) * 8;
+    const uint32_t lo = k == 0 ? w0 : k == 1 ? w1 : w2;
+    const uint32_t hi = k == 0 ? w1 : k == 1 ? w2 : 0u;
+    return sh == 0 ? lo : (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+}
+
+// R = address & 3
+template <int R>
+__device__ __forceinline__ void store_macs(uint8_t* p, uint32_t w0, uint32_t w1, uint32_t w2) {
+    if constexpr (R == 0) {
+        *(gw32_t*)p = w0;
+        *(gw32_t*)(p + 4) = w1;
+        *(gw32_t*)(p + 8) = w2;
+    } else if constexpr (R == 2) {
+        *(gw16_t*)p = (uint16_t)w0;
+        *(gw32_t*)(p + 2) = mac_bytes<2>(w0, w1, w2);
+        *(gw32_t*)(p + 6) = mac_bytes<6>(w0, w1, w2);
+        *(gw16_t*)(p + 10) = (uint16_t)(w2 >> 16);
+    } else if constexpr (R == 1) {   // p + 1 is 2 mod 4
+        *(gw8_t*)p = (uint8_t)w0;
+        *(gw16_t*)(p + 1) = (uint16_t)(w0 >> 8);
+        *(gw32_t*)(p + 3) = mac_bytes<3>(w0, w1, w2);
+        *(gw32_t*)(p + 7) = mac_bytes<7>(w0, w1, w2);
+        *(gw8_t*)(p + 11) = (uint8_t)(w2 >> 24);
+    } else {                         // R == 3: p + 1 is 4-B aligned
+        *(gw8_t*)p = (uint8_t)w0;
+        *(gw32_t*)(p + 1) = mac_bytes<1>(w0, w1, w2);
+        *(gw32_t*)(p + 5) = mac_bytes<5>(w0, w1, w2);
+        *(gw16_t*)(p + 9) = (uint16_t)(w2 >> 8);
+        *(gw8_t*)(p + 11) = (uint8_t)(w2 >> 24);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_l2_forward(uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                   const uint64_t* __restrict__ frame_off,
+                                                   const uint32_t* __restrict__ frame_len,
+                                                   const uint8_t* __restrict__ verdict, const uint8_t* __restrict__ status,
+                                                   const vpcsum_fastpath_t* __restrict__ fp, uint32_t n,
+                                                   uint32_t* __restrict__ port_out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t off = frame_off[i];
+    const uint32_t len = frame_len[i];
+    const uint32_t vd = verdict[i], st = status[i];
+    const u32x4a4_t f = *(g_u32x4a4_t*)(fp + i);   // dst[6] src[6] | port
+    // the frame holds an Ethernet header inside the arena (the sum cannot wrap: off <= arena_len first)
+    const bool inside = len >= 14u && off <= arena_len && (uint64_t)len <= arena_len - off;
+    const bool go = inside && vd == VPCSUM_FLOW_HIT && (st & (VPCSUM_S_DONE | VPCSUM_S_BAD_DESC)) == VPCSUM_S_DONE && f.w != 0u;
+    port_out[i] = go ? f.w : 0u;
+    if (!go) return;
+    uint8_t* p = arena + off;
+    switch ((uint32_t)(uintptr_t)p & 3u) {
+    case 0: store_macs<0>(p, f.x, f.y, f.z); break;
+    case 1: store_macs<1>(p, f.x, f.y, f.z); break;
+    case 2: store_macs<2>(p, f.x, f.y, f.z); break;
+    default: store_macs<3>(p, f.x, f.y, f.z); break;
     }
 }
 
 hipError_t launch_flow_lookup(const void* slots, uint32_t mask, uint32_t max_probe, uint8_t* touched,
                               const vpcsum_tuple_t* tuples, uint32_t n, vpcsum_nat_t* rw_out, uint8_t* verdict_out,
-                              hipStream_t stream) {
+                              vpcsum_fastpath_t* fp_out, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const uint32_t g = (n + 31u) / 32u;   // 256 threads: 32 teams
-    hipLaunchKernelGGL(k_flow_lookup, dim3(g), dim3(256), 0, stream, (const FlowSlot*)slots, mask, max_probe, touched, tuples,
-                       n, rw_out, verdict_out);
+    if (fp_out)
+        hipLaunchKernelGGL(k_flowfp, dim3(g), dim3(256), 0, stream, (const FlowSlot*)slots, mask, max_probe, touched, tuples, n,
+                           rw_out, verdict_out, fp_out);
+    else
+        hipLaunchKernelGGL(k_flow_lookup, dim3(g), dim3(256), 0, stream, (const FlowSlot*)slots, mask, max_probe, touched,
+                           tuples, n, rw_out, verdict_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_l2_forward(uint8_t* arena, uint64_t arena_len, const uint64_t* frame_off, const uint32_t* frame_len,
+                             const uint8_t* verdict, const uint8_t* status, const vpcsum_fastpath_t* fp, uint32_t n,
+                             uint32_t* port_out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_l2_forward, dim3((n + 255u) / 256u), dim3(256), 0, stream, arena, arena_len, frame_off, frame_len,
+                       verdict, status, fp, n, port_out);
     return hipGetLastError();
 }
 

@@ -25,19 +25,23 @@
 namespace vpcsum {
 
 // One slot: 128 B, 128-B aligned, so a probe reads one cache line.  The lookup kernel's team of 8
-// lanes takes 16 B each: lanes 0..2 the key (with the flow id and the occupied word), 3..5 the entry.
+// lanes takes 16 B each: lanes 0..2 the key (with the flow id and the occupied word), 3..5 the entry,
+// lane 7 the flow's Fastpath (port 0: none).
 struct alignas(128) FlowSlot {
     vpcsum_tuple_t key;   //   0: tcp_flags and rsv are 0
     uint32_t flow_id;     //  40: dense, stable for the flow's life, recycled after erase
     uint32_t occupied;    //  44: 0 = empty
     vpcsum_nat_t rw;      //  48
     uint64_t cookie;      //  96
-    uint8_t pad[24];
+    uint8_t pad[8];       // 104
+    vpcsum_fastpath_t fp; // 112: the flow's Ethernet addresses and output port, all zeros = none
 };
 static_assert(sizeof(FlowSlot) == 128 && alignof(FlowSlot) == 128, "one slot is one 128-B line");
 static_assert(offsetof(FlowSlot, flow_id) == 40 && offsetof(FlowSlot, occupied) == 44 && offsetof(FlowSlot, rw) == 48 &&
                   offsetof(FlowSlot, cookie) == 96,
               "FlowSlot layout (flow.hip reads it in 16-B pieces)");
+static_assert(offsetof(FlowSlot, fp) == 112 && sizeof(vpcsum_fastpath_t) == 16,
+              "the Fastpath is the slot's last 16-B piece (flow.hip: lane 7 holds it whole)");
 static_assert(sizeof(vpcsum_flow_t) == 96, "vpcsum_flow_t is 96 bytes");
 
 constexpr int kFlowKeyBytes = 38;   // src[16] dst[16] sport dport l3_ver l4_proto
@@ -167,8 +171,9 @@ public:
         return true;
     }
 
-    // Insert, or replace the rewrite and cookie of a key already there (its id stays).  The flow id,
-    // or -1 with *why set and nothing changed.  Slots written are noted in `dirty`.
+    // Insert, or replace the rewrite and cookie of a key already there (its id and its Fastpath
+    // stay); a new flow has no Fastpath.  The flow id, or -1 with *why set and nothing changed.
+    // Slots written are noted in `dirty`.
     int64_t insert(const vpcsum_flow_t& f, FlowDirty* dirty, const char** why = nullptr) {
         if (const char* r = flow_key_refusal(f.key)) {
             if (why) *why = r;
@@ -211,7 +216,24 @@ public:
         return -1;
     }
 
-    // Erase by backward shift; the erased flow's id (now free), or -1 when the key is not there.
+    // The Fastpath of a key: 1 = set (port 0: cleared, the slot's record all zeros), 0 = the key is
+    // not there, -1 = a malformed key (*why set); nothing changes unless 1.  Allocates nothing.
+    int set_fastpath(const vpcsum_tuple_t& key, const vpcsum_fastpath_t& fp, FlowDirty* dirty, const char** why = nullptr) {
+        if (const char* r = flow_key_refusal(key)) {
+            if (why) *why = r;
+            return -1;
+        }
+        const int64_t at = find(key);
+        if (at < 0) return 0;
+        FlowSlot& s = slot_[at];
+        if (fp.port != 0) s.fp = fp;
+        else memset(&s.fp, 0, sizeof(s.fp));
+        if (dirty) dirty->note((uint32_t)at);
+        return 1;
+    }
+
+    // Erase by backward shift (a shifted flow's Fastpath moves with its slot, the erased one's
+    // goes); the erased flow's id (now free), or -1 when the key is not there.
     int64_t erase(const vpcsum_tuple_t& key, FlowDirty* dirty) {
         const int64_t at = find(key);
         if (at < 0) return -1;

@@ -98,10 +98,15 @@ hipError_t launch_parse_ether(const uint8_t* arena, uint64_t arena_len, const ui
 
 // NAT flow table lookup (flow.hip): tuples[i] looked up in `slots` (mask + 1 FlowSlot of
 // flow_table.h, probes of at most max_probe + 1 slots): verdict_out[i] = VPCSUM_FLOW_*, rw_out[i] the
-// flow's entry on a HIT and 48 zero bytes otherwise, touched[flow id] = 1 on a HIT.
+// flow's entry on a HIT and 48 zero bytes otherwise, touched[flow id] = 1 on a HIT.  fp_out != NULL:
+// the kernel that also writes fp_out[i], the flow's Fastpath on a HIT and 16 zero bytes otherwise.
 hipError_t launch_flow_lookup(const void* slots, uint32_t mask, uint32_t max_probe, uint8_t* touched,
                               const vpcsum_tuple_t* tuples, uint32_t n, vpcsum_nat_t* rw_out, uint8_t* verdict_out,
-                              hipStream_t stream);
+                              vpcsum_fastpath_t* fp_out, hipStream_t stream);
+// The L2 write after a lookup and a rewrite (flow.hip, vpcsum.h vpcsum_l2_forward_async's rule)
+hipError_t launch_l2_forward(uint8_t* arena, uint64_t arena_len, const uint64_t* frame_off, const uint32_t* frame_len,
+                             const uint8_t* verdict, const uint8_t* status, const vpcsum_fastpath_t* fp, uint32_t n,
+                             uint32_t* port_out, hipStream_t stream);
 
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t grid, hipStream_t stream);
 hipError_t launch_pattern_probe(const uint8_t* arena, uint64_t arena_len, const void* desc, uint32_t n, uint32_t* sink,

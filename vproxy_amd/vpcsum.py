@@ -48,6 +48,8 @@ HSUM_DTYPE = np.dtype([("sum", "<u2"), ("l4_len", "<u2"), ("hlen", "u1"), ("l4_p
 # vpcsum_flow_t: one flow of the NAT flow table -- key (tcp_flags / rsv 0), rewrite, caller's cookie
 FLOW_DTYPE = np.dtype([("key", TUPLE_DTYPE), ("rw", NAT_DTYPE), ("cookie", "<u8")])
 FLOW_MISS, FLOW_HIT, FLOW_PUNT = 0, 1, 2
+# vpcsum_fastpath_t: a flow's Ethernet addresses (wire order) and output port; port 0 = no Fastpath
+FASTPATH_DTYPE = np.dtype([("dst", "u1", 6), ("src", "u1", 6), ("port", "<u4")])
 
 # Every symbol include/vpcsum.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -79,6 +81,9 @@ EXPORTS = [
     "Java_io_vproxy_vpcsum_VPCsum_flowtabCreate", "Java_io_vproxy_vpcsum_VPCsum_flowtabUpdate",
     "Java_io_vproxy_vpcsum_VPCsum_flowtabCollect", "Java_io_vproxy_vpcsum_VPCsum_flowtabClose",
     "Java_io_vproxy_vpcsum_VPCsum_natFlowFrames",
+    "vpcsum_flowtab_set_fastpath", "vpcsum_flow_lookup_fp_async", "vpcsum_l2_forward_async",
+    "vpcsum_ctx_nat_flow_forward_frames", "Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath",
+    "Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames",
 ]
 
 
@@ -251,6 +256,10 @@ def _declare(L):
         "vpcsum_flow_lookup_async": ([P, P, U32, P, P, P], I),
         "vpcsum_flowtab_collect": ([P, P, U32, P, P], I),
         "vpcsum_ctx_nat_flow_frames": ([P, P, P, U64, P, P, U32, P, P, U32, P], I),
+        "vpcsum_flowtab_set_fastpath": ([P, P, P, U32, P, P], I),
+        "vpcsum_flow_lookup_fp_async": ([P, P, U32, P, P, P, P], I),
+        "vpcsum_l2_forward_async": ([P, U64, P, P, P, P, P, U32, P, P], I),
+        "vpcsum_ctx_nat_flow_forward_frames": ([P, P, P, U64, P, P, U32, P, P, P, U32, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -486,6 +495,20 @@ def flow_hash(key) -> int:
     return h.value
 
 
+def l2_forward(arena, frame_off, frame_len, verdict, status, fastpath, n: int, port, stream=None):
+    """vpcsum_l2_forward_async on device tensors: `arena` uint8, `frame_off` n x uint64, `frame_len`
+    n x uint32, `verdict` / `status` n bytes, `fastpath` n x 16 bytes, `port` n x uint32 (written).
+    A frame gets its record's addresses in bytes [0,12) and its port only when its verdict is
+    FLOW_HIT, its status S_DONE without S_BAD_DESC and the record's port not 0."""
+    assert verdict.numel() >= n and status.numel() >= n
+    assert frame_off.numel() * frame_off.element_size() >= n * 8 and frame_len.numel() * frame_len.element_size() >= n * 4
+    assert fastpath.numel() * fastpath.element_size() >= n * FASTPATH_DTYPE.itemsize
+    assert port.numel() * port.element_size() >= n * 4
+    _check(lib().vpcsum_l2_forward_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(frame_off), _ptr(frame_len),
+                                         _ptr(verdict), _ptr(status), _ptr(fastpath), n, _ptr(port), _stream(stream)),
+           "vpcsum_l2_forward_async")
+
+
 class FlowTable:
     """The NAT flow table on one device (vpcsum_flowtab_*): TUPLE_DTYPE key -> NAT_DTYPE rewrite,
     updated from the host, looked up on the GPU (lookup, Context.nat_flow_frames)."""
@@ -506,13 +529,36 @@ class FlowTable:
                                            a.ctypes.data if len(a) else None, len(a), _stream(stream)),
                "vpcsum_flowtab_update")
 
-    def lookup(self, tuples, n: int, rw, verdict, stream=None):
+    def set_fastpath(self, keys, fps, stream=None) -> int:
+        """vpcsum_flowtab_set_fastpath: the Fastpath of each TUPLE_DTYPE key present becomes its
+        FASTPATH_DTYPE record (port 0 clears it); returns how many keys were not in the table.  A
+        malformed key raises and changes nothing.  Ordered on `stream` as update."""
+        k = np.ascontiguousarray(np.asarray(keys, TUPLE_DTYPE).reshape(-1))
+        f = np.ascontiguousarray(np.asarray(fps, FASTPATH_DTYPE).reshape(-1))
+        assert len(k) == len(f)
+        missing = ctypes.c_uint32()
+        _check(lib().vpcsum_flowtab_set_fastpath(self.h, k.ctypes.data if len(k) else None, f.ctypes.data if len(f) else None,
+                                                 len(k), ctypes.byref(missing), _stream(stream)),
+               "vpcsum_flowtab_set_fastpath")
+        return missing.value
+
+    def lookup(self, tuples, n: int, rw, verdict, stream=None, fastpath=None):
         """vpcsum_flow_lookup_async: `tuples` n x 40 bytes, `rw` n x 48 bytes and `verdict` n bytes,
-        uint8 device tensors."""
+        uint8 device tensors.  With `fastpath` (n x 16 bytes) vpcsum_flow_lookup_fp_async: each
+        flow's FASTPATH_DTYPE record too (fastpath=True: a new tensor, which is returned)."""
         assert tuples.numel() * tuples.element_size() >= n * TUPLE_DTYPE.itemsize
         assert rw.numel() * rw.element_size() >= n * NAT_DTYPE.itemsize and verdict.numel() >= n
-        _check(lib().vpcsum_flow_lookup_async(self.h, _ptr(tuples), n, _ptr(rw), _ptr(verdict), _stream(stream)),
-               "vpcsum_flow_lookup_async")
+        if fastpath is None or fastpath is False:
+            _check(lib().vpcsum_flow_lookup_async(self.h, _ptr(tuples), n, _ptr(rw), _ptr(verdict), _stream(stream)),
+                   "vpcsum_flow_lookup_async")
+            return None
+        if fastpath is True:
+            import torch
+            fastpath = torch.zeros(max(n, 1) * FASTPATH_DTYPE.itemsize, dtype=torch.uint8, device=verdict.device)
+        assert fastpath.numel() * fastpath.element_size() >= n * FASTPATH_DTYPE.itemsize
+        _check(lib().vpcsum_flow_lookup_fp_async(self.h, _ptr(tuples), n, _ptr(rw), _ptr(verdict), _ptr(fastpath),
+                                                 _stream(stream)), "vpcsum_flow_lookup_fp_async")
+        return fastpath
 
     def collect(self, cap: int | None = None, stream=None):
         """Cookies of the flows hit since the last collect (marks cleared).  With `cap`, a count
@@ -699,6 +745,26 @@ class Context:
                                                 ctypes.byref(t)), "vpcsum_ctx_nat_flow_frames")
         self.wait(t.value)
         return status, verdict
+
+    def nat_flow_forward_frames(self, tab: "FlowTable", arena: np.ndarray, frame_off: np.ndarray, frame_len: np.ndarray,
+                                nat_mode: int = NAT_RFC1624):
+        """nat_flow_frames that also forwards (vpcsum_ctx_nat_flow_forward_frames): a HIT frame that
+        was rewritten and whose flow has a Fastpath gets the flow's Ethernet addresses written and
+        its port returned.  Returns (status, verdict, port) per frame; port 0: the frame's Ethernet
+        header is as received."""
+        n = len(frame_off)
+        fo = np.ascontiguousarray(frame_off, dtype=np.uint64)
+        fl = np.ascontiguousarray(frame_len, dtype=np.uint32)
+        status = np.zeros(n, np.uint8)
+        verdict = np.zeros(n, np.uint8)
+        port = np.zeros(n, np.uint32)
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_nat_flow_forward_frames(self.h, tab.h, arena.ctypes.data, arena.nbytes, fo.ctypes.data,
+                                                        fl.ctypes.data, n, status.ctypes.data, verdict.ctypes.data,
+                                                        port.ctypes.data, nat_mode, ctypes.byref(t)),
+               "vpcsum_ctx_nat_flow_forward_frames")
+        self.wait(t.value)
+        return status, verdict, port
 
     def set_service(self, idle_us: int):
         """Low-latency flushes from registered arenas (persistent service grid); 0 = off."""
