@@ -47,7 +47,9 @@ extern "C" {
  * the context has not registered instead of copying from it directly.
  * Additive since (the version stays 4): VPCSUM_NAT_TCP entries under the nat_mode bit
  * VPCSUM_NAT_TCP_REWRITES; a library from before answers that bit with "bad nat_mode", which is
- * how a caller probes for it. */
+ * how a caller probes for it; the flow table and its Fastpath; the TCP segment build
+ * (vpcsum_tcp_build_async, vpcsum_ctx_build_tcp_frames, VPCsum.buildTcpFrames): new symbols, which a
+ * caller probes for by looking them up. */
 #define VPCSUM_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -426,6 +428,70 @@ int vpcsum_l2_forward_async(uint8_t* d_arena, uint64_t arena_len, const uint64_t
                             const uint32_t* d_frame_len, const uint8_t* d_verdict, const uint8_t* d_status,
                             const vpcsum_fastpath_t* d_fp, uint32_t n, uint32_t* d_port, void* stream);
 
+/* TCP segment build (additive, the ABI version stays 4): what the userspace TCP stack does on the
+ * host for every segment it sends (TcpStack.transmitTcpPsh -> sendTcpPsh, TcpStack.java:469-503,
+ * 553-566: TcpUtils.buildCommonTcpResponse / buildIpResponse, TcpUtils.java:15-57; on the Fastpath
+ * a new Ethernet header, L4Output.java:56-72, Fastpath.java:24-47; XDPIface.sendPacket's copy into
+ * a umem chunk), as one fused copy-and-checksum: "connection header + payload run" in, finished
+ * frames out.  The payload is read once from the send buffer and written once into the frame, the
+ * TCP sum accumulated on the way, the headers generated from the template; the result equals
+ * getRawPacket(0) of what sendTcpPsh / sendTcpFin / buildAckResponse / buildRstResponse build.
+ * SYNs carry options and stay on the host.  Fields marked "wire" are network order, exactly the
+ * bytes written into the frame. */
+typedef struct vpcsum_tcphdr {     /* one per connection direction; 64 bytes */
+    uint8_t  eth_dst[6];   /*  0  Fastpath.remote  (frame bytes [0,6))  */
+    uint8_t  eth_src[6];   /*  6  Fastpath.local   (frame bytes [6,12)) */
+    uint8_t  l2_len;       /* 12  14: Ethernet header written, EtherType from l3_ver (0x0800 / 0x86dd,
+                                  Fastpath.java:39-43); 0: the frame starts at the IP header (L4Output's ip-output edge) */
+    uint8_t  l3_ver;       /* 13  4 / 6 */
+    uint8_t  tos;          /* 14  IPv4 byte 1 (dscp<<2|ecn) / IPv6 traffic class; the stack uses 0 */
+    uint8_t  ttl;          /* 15  TTL / hop limit; the stack uses 64 */
+    uint8_t  src[16];      /* 16  IPv4: first 4 bytes, the rest ignored */
+    uint8_t  dst[16];      /* 32 */
+    uint8_t  sport[2];     /* 48  wire */
+    uint8_t  dport[2];     /* 50  wire */
+    uint8_t  ack[4];       /* 52  wire */
+    uint8_t  window[2];    /* 56  wire */
+    uint8_t  ident[2];     /* 58  IPv4 identification, wire (the stack: 0); ignored for IPv6 */
+    uint8_t  frag[2];      /* 60  IPv4 flags<<13 | fragment offset, wire (the stack: 0); ignored for IPv6 */
+    uint8_t  rsv[2];       /* 62  must be 0 */
+} vpcsum_tcphdr_t;
+
+typedef struct vpcsum_tcpseg {     /* one per frame to build; 32 bytes */
+    uint64_t frame_off;    /*  0  where the frame starts in the destination arena, any alignment */
+    uint64_t data_off;     /*  8  where the payload starts in the source arena, any alignment */
+    uint32_t seq;          /* 16  host order; written big-endian */
+    uint32_t hdr;          /* 20  index into the header array */
+    uint32_t frame_cap;    /* 24  room at frame_off (the chunk's); a frame that needs more is refused */
+    uint16_t data_len;     /* 28  0 for ACK / FIN / RST */
+    uint8_t  flags;        /* 30  TCP flags, low 6 bits (TcpPacket.setFlags) */
+    uint8_t  rsv;          /* 31  must be 0 */
+} vpcsum_tcpseg_t;
+
+/* Frame i, of length L = l2_len + (20 | 40) + 20 + data_len, at d_dst + frame_off:
+ *   Ethernet (l2_len 14): eth_dst, eth_src, EtherType.
+ *   IPv4 (Ipv4Packet.genHeaderWithChecksumUnfilled :279-294, IHL 5): 45, tos, totalLength 40 +
+ *     data_len, ident, frag, ttl, 06, the header sum (Utils.calculateChecksum over the 20 bytes),
+ *     src[0..3], dst[0..3].
+ *   IPv6 (Ipv6Packet.buildPacket :185-190, no extension headers, flow label 0): 60 | tos>>4,
+ *     (tos<<4) & 0xff, 00 00, payloadLength 20 + data_len, 06, ttl, src, dst.
+ *   TCP (TcpPacket.buildCommonPart :394-452, no options): sport, dport, seq, ack, 50, flags, window,
+ *     the TCP sum (pseudo-header and segment; 0x0000 is stored as it is), urgent pointer 00 00, the
+ *     data_len payload bytes from d_src + data_off.
+ * A record is refused -- d_frame_len[i] 0, d_out[i] 0, S_BAD_DESC, not one byte written, nothing read
+ * but the record and its template -- when hdr >= n_hdr; the template's l3_ver is not 4 / 6, its l2_len
+ * not 0 / 14 or its rsv not 0; flags & ~0x3f or the record's rsv != 0; L > frame_cap; 40 + data_len
+ * (IPv4) or 20 + data_len (IPv6) > 65535 (Java would silently truncate the length field: the build
+ * refuses); frame_off + L > dst_len or data_off + data_len > src_len (both checked without wrapping).
+ * Otherwise d_frame_len[i] = L (required), d_out[i] (may be NULL) holds the IPv4 header sum in bits
+ * 0..15 (0 for IPv6) and the TCP sum in bits 16..31, d_status[i] (may be NULL) S_DONE.
+ * Templates and frame lengths 4-byte aligned, records 8-byte aligned; n at most 2^28; n == 0 returns 0.
+ * Frames of one batch must not overlap each other or any payload range: the caller's rule, as for the
+ * NAT submits. */
+int vpcsum_tcp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_src, uint64_t src_len,
+                           const vpcsum_tcphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* d_seg, uint32_t n,
+                           uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream);
+
 /* Streaming-read ceiling probe: reads `bytes` from d_buf with 16-B lanes, writes one word per
  * block into d_sink.  Used by bench.py to report a measured HBM read roof next to 8 TB/s. */
 int vpcsum_read_probe_async(const uint8_t* d_buf, uint64_t bytes, uint32_t* d_sink,
@@ -583,6 +649,19 @@ int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* ctx, vpcsum_flowtab_t* tab,
                                        const uint64_t* h_frame_off, const uint32_t* h_frame_len, uint32_t n,
                                        uint8_t* h_status, uint8_t* h_verdict, uint32_t* h_port, uint32_t nat_mode,
                                        uint64_t* ticket);
+/* vpcsum_tcp_build_async from host memory, in one submission: the frames are written where they lie
+ * in h_dst, which must be inside a REGISTERED arena (the TX umem; an unregistered destination is
+ * refused, like vpcsum_ctx_nat_flow_frames).  A registered h_src is read in place; any other is staged:
+ * the span [min data_off, max data_off + data_len) over the batch's records with a payload inside
+ * src_len goes to the device in one copy (refused if larger than the context's max_arena_bytes) and
+ * the kernel reads that copy, data_off rebased in the library's own copy of the records -- the
+ * caller's array is not written.  n and n_hdr are each at most the context's max_pkts.  At
+ * vpcsum_ctx_wait h_frame_len[i] (required), h_out[i] and h_status[i] (each may be NULL) hold what
+ * vpcsum_tcp_build_async writes.  The batch is always launched: there is no service-grid,
+ * device-group or process-wide form. */
+int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* ctx, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
+                                const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* h_seg, uint32_t n,
+                                uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket);
 /* The egress flush of a batch holding NAT'd frames: vpcsum_ctx_submit where
  * descriptors with VPCSUM_F_PRE take their L4 sum from h_pre[i] (pre_fmt as vpcsum_pre_async;
  * entries of other descriptors are ignored) and the others are summed in full, in one submission.
@@ -748,6 +827,12 @@ int Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath(PNIEnv_vpcsum_int* env, int6
 int Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames(PNIEnv_vpcsum_long* env, int64_t ctx, int64_t tab, void* arena,
                                                       int64_t arenaLen, void* frameOff, void* frameLen, int32_t n,
                                                       void* status, void* verdict, void* port, int32_t natMode);
+/* VPCsum.buildTcpFrames(long ctx, MemorySegment dst, long dstLen, MemorySegment src, long srcLen,
+ *                       MemorySegment hdr, int nHdr, MemorySegment seg, int n, MemorySegment frameLen,
+ *                       MemorySegment out, MemorySegment status) -> long ticket (vpcsum_ctx_build_tcp_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
+                                                int64_t srcLen, void* hdr, int32_t nHdr, void* seg, int32_t n,
+                                                void* frameLen, void* out, void* status);
 /* VPCsum.setService(long ctx, int idleUs) */
 int Java_io_vproxy_vpcsum_VPCsum_setService(PNIEnv_vpcsum_void* env, int64_t ctx, int32_t idleUs);
 /* VPCsum.waitFor(long ctx, long ticket) */

@@ -398,6 +398,24 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * The data segments of the userspace TCP stack (TcpStack.transmitTcpPsh's loop over
+     * sendingQueue.fetch(), and its FIN / ACK / RST answers) built on the GPU straight into TX chunks
+     * of the umem: {@code count} records ({@link VPCsum#tcpSeg}: one per Segment, seq =
+     * seqBeginInclusive, flags PSH|ACK; dataLen 0 for FIN / ACK / RST) over {@code nHdr} templates
+     * ({@link VPCsum#tcpHdr}: one per TcpEntry direction), payloads read from {@code sendBuf} (in
+     * place when it is registered, staged otherwise).  Fills {@code frameLenOut} (u32 per record): the
+     * frame's length for the TX descriptor, or 0 -- the record was refused, build that segment on the
+     * host.  SYNs carry options and stay on the host.
+     */
+    public MemorySegment buildTcp(MemorySegment sendBuf, long sendBufLen, MemorySegment hdr, int nHdr, MemorySegment seg, int count,
+                                  MemorySegment frameLenOut, MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().buildTcpFrames(env, ctx, umem, umemLen, sendBuf, sendBufLen, hdr, nHdr, seg, count, frameLenOut,
+            MemorySegment.NULL, statusOut);
+        VPCsum.get().waitFor(env, ctx, t);
+        return frameLenOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

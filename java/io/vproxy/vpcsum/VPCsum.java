@@ -121,6 +121,64 @@ public class VPCsum {
         rw.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 47, (byte) 0);
     }
 
+    /** bytes of one vpcsum_tcphdr_t header template ({@link #tcpHdr}) */
+    public static final int TCP_HDR = 64;
+    /** bytes of one vpcsum_tcpseg_t record ({@link #tcpSeg}) */
+    public static final int TCP_SEG = 32;
+
+    /** Fill the 64-byte header template at {@code hdr[off..]} for one direction of a TcpEntry, as
+     * TcpUtils.buildCommonTcpResponse / buildIpResponse read it at the moment of the batch:
+     * {@code fastpathRemote} / {@code fastpathLocal} the entry's Fastpath addresses (6 bytes each; null:
+     * no Ethernet header, the frame starts at the IP header), {@code src} / {@code dst} 4 or 16 address
+     * bytes (tcp.local / tcp.remote), ports, {@code ack} (receivingQueue.getAckedSeq()) and {@code window}
+     * (receivingQueue.getWindow() / scale) as the ints Java passes to setAckNum / setWindow.  tos 0,
+     * TTL / hop limit 64, identification and fragment word 0: what the stack uses. */
+    public static void tcpHdr(MemorySegment hdr, long off, byte[] fastpathRemote, byte[] fastpathLocal, byte[] src, byte[] dst,
+                              int sport, int dport, int ack, int window) {
+        final var B = java.lang.foreign.ValueLayout.JAVA_BYTE;
+        hdr.asSlice(off, TCP_HDR).fill((byte) 0);
+        boolean eth = fastpathRemote != null && fastpathLocal != null;
+        for (int i = 0; eth && i < 6; ++i) {
+            hdr.set(B, off + i, fastpathRemote[i]);
+            hdr.set(B, off + 6 + i, fastpathLocal[i]);
+        }
+        hdr.set(B, off + 12, (byte) (eth ? 14 : 0));
+        hdr.set(B, off + 13, (byte) (src.length == 4 ? 4 : 6));
+        hdr.set(B, off + 15, (byte) 64);
+        for (int i = 0; i < src.length; ++i) {
+            hdr.set(B, off + 16 + i, src[i]);
+            hdr.set(B, off + 32 + i, dst[i]);
+        }
+        hdr.set(B, off + 48, (byte) (sport >> 8));
+        hdr.set(B, off + 49, (byte) sport);
+        hdr.set(B, off + 50, (byte) (dport >> 8));
+        hdr.set(B, off + 51, (byte) dport);
+        hdr.set(B, off + 52, (byte) (ack >> 24));
+        hdr.set(B, off + 53, (byte) (ack >> 16));
+        hdr.set(B, off + 54, (byte) (ack >> 8));
+        hdr.set(B, off + 55, (byte) ack);
+        hdr.set(B, off + 56, (byte) (window >> 8));
+        hdr.set(B, off + 57, (byte) window);
+    }
+
+    /** Fill the 32-byte record at {@code seg[off..]}: the frame goes to {@code frameOff} of the
+     * destination arena (room {@code frameCap} there), its {@code dataLen} payload bytes come from
+     * {@code dataOff} of the source arena, {@code seq} is Segment.seqBeginInclusive (or the sequence
+     * number of a FIN / ACK / RST, dataLen 0), {@code hdrIndex} the template, {@code flags} the TCP
+     * flags (Consts.TCP_FLAGS_*, low 6 bits). */
+    public static void tcpSeg(MemorySegment seg, long off, long frameOff, long dataOff, int seq, int hdrIndex, int frameCap,
+                              int dataLen, int flags) {
+        final var LE = java.nio.ByteOrder.LITTLE_ENDIAN;
+        seg.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off, frameOff);
+        seg.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off + 8, dataOff);
+        seg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 16, seq);
+        seg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 20, hdrIndex);
+        seg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 24, frameCap);
+        seg.set(java.lang.foreign.ValueLayout.JAVA_SHORT_UNALIGNED.withOrder(LE), off + 28, (short) dataLen);
+        seg.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 30, (byte) (flags & 0x3f));
+        seg.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 31, (byte) 0);
+    }
+
     private static final MethodHandle createMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
         "Java_io_vproxy_vpcsum_VPCsum_create", int.class /* device */, long.class /* maxArena */, int.class /* maxPkts */);
 
@@ -525,6 +583,37 @@ public class VPCsum {
         try {
             ERR = (int) natFlowForwardFramesMH.invokeExact(ENV.MEMORY, ctx, tab, arena, arenaLen, frameOff, frameLen, n, status, verdict,
                 port, natMode);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    private static final MethodHandle buildTcpFramesMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames", long.class /* ctx */, MemorySegment.class /* dst */, long.class /* dstLen */,
+        MemorySegment.class /* src */, long.class /* srcLen */, MemorySegment.class /* hdr */, int.class /* nHdr */,
+        MemorySegment.class /* seg */, int.class /* n */, MemorySegment.class /* frameLen */, MemorySegment.class /* out */,
+        MemorySegment.class /* status */);
+
+    /** The TCP segment build (vpcsum_ctx_build_tcp_frames): {@code n} records of {@link #TCP_SEG} bytes
+     * ({@link #tcpSeg}) over {@code nHdr} templates of {@link #TCP_HDR} bytes ({@link #tcpHdr}); each
+     * frame -- Ethernet, IP and TCP headers with both sums, then the payload copied from {@code src} --
+     * is written at its frameOff of {@code dst}, which must lie in a registered arena (the TX umem).  A
+     * registered {@code src} is read in place, any other staged.  After {@link #waitFor}:
+     * frameLen[i] (u32) the frame's length, 0 for a refused record (status[i] S_BAD_DESC, nothing
+     * written); out / status may be MemorySegment.NULL.  SYNs carry options: build them on the host. */
+    public long buildTcpFrames(PNIEnv ENV, long ctx, MemorySegment dst, long dstLen, MemorySegment src, long srcLen,
+                               MemorySegment hdr, int nHdr, MemorySegment seg, int n, MemorySegment frameLen, MemorySegment out,
+                               MemorySegment status) throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) buildTcpFramesMH.invokeExact(ENV.MEMORY, ctx, dst, dstLen, src, srcLen, hdr, nHdr, seg, n, frameLen, out,
+                status);
         } catch (Throwable THROWABLE) {
             throw PanamaUtils.convertInvokeExactException(THROWABLE);
         }

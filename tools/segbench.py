@@ -1,0 +1,135 @@
+"""The TCP segment build, device-resident: N data segments of 1,360 bytes (TcpEntry.SND_DEFAULT_MSS)
+and of 1,460 bytes, payloads back to back in a send buffer, built as Ethernet / IPv4 / TCP frames into
+2,048-byte chunks at chunk + 384 (umem geometry: the payload lands at chunk + 438).  Timed with events
+over --launches launches after a warm-up, legs in alternating rounds:
+  a  vpcsum_tcp_build_async (k_tcp_build): headers, copy and both sums in one pass
+  b  today's device equivalent from the entry points that existed before it: hipMemcpy2DAsync of the
+     payloads into frames whose headers are already there, then vpcsum_compute_async with MODE_WRITE
+     over the frames (descriptors prepared once, outside the timed window)
+  c  that 2-D copy alone: the copy ceiling
+  d  for scale, a contiguous device copy of the same payload bytes (no frames): what moving
+     2 x data_len bytes per segment costs when nothing is strided
+Algorithmic bytes per segment: data_len read + L written + the 32-byte record.  Before timing, b's
+frames are compared with a's: the two must build the same bytes.
+Prints one JSON line.  usage: segbench.py [segments] [--launches N]"""
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vproxy_amd import vpcsum as V  # noqa: E402
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 1 << 17
+launches = int(sys.argv[sys.argv.index("--launches") + 1]) if "--launches" in sys.argv else 50
+rounds = 3
+STRIDE, HEADROOM, HLEN = 2048, 384, 54
+
+V.lib()
+hip = None
+with open("/proc/self/maps") as f:
+    for line in f:
+        if "libamdhip64.so" in line:
+            hip = ctypes.CDLL(line.split()[-1])
+            break
+assert hip is not None, "libamdhip64 is not loaded"
+hip.hipMemcpy2DAsync.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                 ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+hip.hipMemcpy2DAsync.restype = ctypes.c_int
+D2D = 3   # hipMemcpyDeviceToDevice
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).pin_memory().cuda()
+
+
+def timed(fn):
+    for _ in range(3):
+        fn()
+    e0, e1 = V.Event(), V.Event()
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_ms(e1) / launches * 1e3   # us per launch
+
+
+hdr = np.zeros(1, V.TCPHDR_DTYPE)
+hdr["eth_dst"], hdr["eth_src"] = np.frombuffer(bytes.fromhex("02aa00000001"), np.uint8), np.frombuffer(bytes.fromhex("02bb00000002"), np.uint8)
+hdr["l2_len"], hdr["l3_ver"], hdr["ttl"] = 14, 4, 64
+hdr["src"][0, :4], hdr["dst"][0, :4] = (10, 0, 0, 1), (10, 0, 0, 2)
+hdr["sport"], hdr["dport"] = np.frombuffer((43210).to_bytes(2, "big"), np.uint8), np.frombuffer((443).to_bytes(2, "big"), np.uint8)
+hdr["ack"], hdr["window"] = np.frombuffer((0x01020304).to_bytes(4, "big"), np.uint8), np.frombuffer((65535).to_bytes(2, "big"), np.uint8)
+d_hdr = dev(hdr)
+
+res = {"segments": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
+       "frames": "Ethernet / IPv4 / TCP, PSH|ACK"}
+for data_len in (1360, 1460):
+    L = HLEN + data_len
+    seg = np.zeros(n, V.TCPSEG_DTYPE)
+    seg["frame_off"] = np.arange(n, dtype=np.uint64) * STRIDE + HEADROOM
+    seg["data_off"] = np.arange(n, dtype=np.uint64) * data_len
+    seg["seq"] = (np.arange(n, dtype=np.uint64) * data_len & 0xffffffff).astype(np.uint32)
+    seg["frame_cap"], seg["data_len"], seg["flags"] = STRIDE - HEADROOM, data_len, 0x18
+    d_seg = dev(seg)
+    g = torch.Generator(device="cuda").manual_seed(data_len)
+    src = torch.randint(0, 256, (n * data_len,), dtype=torch.uint8, device="cuda", generator=g)
+    dst = torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda")
+    flen = torch.zeros(n, dtype=torch.int32, device="cuda")
+    out = torch.zeros(n, dtype=torch.int32, device="cuda")
+    st = torch.zeros(n, dtype=torch.uint8, device="cuda")
+
+    def leg_a():
+        V.tcp_build(dst, src, d_hdr, 1, d_seg, n, flen, out, st)
+
+    leg_a()
+    torch.cuda.synchronize()
+    assert int((st != V.S_DONE).sum().item()) == 0 and int((flen != L).sum().item()) == 0
+    built = dst.clone()
+    # b's frames: the headers a wrote (sums and all), payload bytes cleared; descriptors once
+    dst2 = built.clone()
+    dst2.view(n, STRIDE)[:, HEADROOM + HLEN:HEADROOM + L] = 0
+    foff = dev(seg["frame_off"].copy())
+    desc = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+    V.parse_ether(dst2, foff, flen, n, desc)
+    out2 = torch.zeros(n, dtype=torch.int32, device="cuda")
+    st2 = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def leg_c():
+        rc = hip.hipMemcpy2DAsync(dst2.data_ptr() + HEADROOM + HLEN, STRIDE, src.data_ptr(), data_len, data_len, n, D2D, stream)
+        assert rc == 0, rc
+
+    def leg_b():
+        leg_c()
+        V.compute(dst2, desc, n, out2, st2, V.MODE_WRITE)
+
+    leg_b()
+    torch.cuda.synchronize()
+    assert torch.equal(dst2, built) and torch.equal(out2, out), "b builds a's frames"
+    flat = torch.empty_like(src)
+
+    def leg_d():
+        flat.copy_(src)
+
+    legs = {"a_tcp_build": leg_a, "b_copy2d_plus_compute_write": leg_b, "c_copy2d_alone": leg_c, "d_contiguous_copy": leg_d}
+    us = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            us[k].append(round(timed(fn), 2))
+    assert torch.equal(dst, built) and torch.equal(dst2, built)
+    bytes_per_seg = data_len + L + 32
+    r = {"frame_len": L, "algorithmic_bytes_per_segment": bytes_per_seg}
+    for k, v in us.items():
+        med = sorted(v)[len(v) // 2]
+        r[k] = {"us_rounds": v, "us_median": med, "Mseg_per_s": round(n / med, 2), "GB_per_s": round(n * bytes_per_seg / med / 1e3, 1)}
+    r["b_over_a"] = round(r["b_copy2d_plus_compute_write"]["us_median"] / r["a_tcp_build"]["us_median"], 3)
+    r["a_over_c"] = round(r["a_tcp_build"]["us_median"] / r["c_copy2d_alone"]["us_median"], 3)
+    res[f"data_len_{data_len}"] = r
+    r["d_contiguous_copy"]["GB_per_s"] = round(n * 2 * data_len / r["d_contiguous_copy"]["us_median"] / 1e3, 1)   # its own bytes
+    del src, dst, dst2, built, flat
+print(json.dumps(res))

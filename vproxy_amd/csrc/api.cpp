@@ -25,6 +25,7 @@
 #include "batch_plan.h"
 #include "flow_table.h"
 #include "internal.h"
+#include "tcp_build.h"
 #include "vpcsum.h"
 
 namespace vpcsum {
@@ -143,6 +144,7 @@ struct Batch {
     vpcsum_hsum_t* user_hsum = nullptr;       // verify batch with header sums: where they go
     uint8_t* user_verdict = nullptr;          // flow batch (vpcsum_ctx_nat_flow_frames): where the verdicts go
     uint32_t* user_port = nullptr;            // forwarding flow batch: where the output ports go
+    uint32_t* user_flen = nullptr;            // TCP build batch (vpcsum_ctx_build_tcp_frames): where the frame lengths go
 };
 
 // Per-slot staging of one in-flight batch of a context.
@@ -165,6 +167,9 @@ struct Slot {
     Mapped<uint8_t> h_verdict;         // with the context's first flow batch
     vpcsum_fastpath_t* d_fp = nullptr; // a forwarding flow batch's Fastpath records (lookup -> L2 write, device only)
     Mapped<uint32_t> h_port;           // and its output ports: with the context's first such batch
+    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records, templates and frame lengths: with the
+    Mapped<vpcsum_tcphdr_t> h_thdr;    // context's first such batch
+    Mapped<uint32_t> h_tlen;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool busy = false;                 // `batch` is in flight
@@ -694,6 +699,9 @@ static void slot_free(Slot& s) {
     s.h_verdict.free();
     if (s.d_fp) (void)hipFree(s.d_fp);
     s.h_port.free();
+    s.h_tseg.free();
+    s.h_thdr.free();
+    s.h_tlen.free();
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = Slot();
@@ -976,6 +984,7 @@ static int slot_finish(vpcsum_ctx* c, Slot& s) {
     if (b.user_status) memcpy(b.user_status, res_status, b.n);
     if (b.user_verdict) memcpy(b.user_verdict, s.h_verdict.p, b.n);
     if (b.user_port) memcpy(b.user_port, s.h_port.p, (size_t)b.n * 4);
+    if (b.user_flen) memcpy(b.user_flen, s.h_tlen.p, (size_t)b.n * 4);
     switch (b.kind) {
     case BatchKind::Nat:
         // a staged batch's rewritten headers (L3 header through the L4 checksum field; the TCP
@@ -1781,6 +1790,28 @@ int vpcsum_l2_forward_async(uint8_t* d_arena, uint64_t arena_len, const uint64_t
     } VPC_CATCH("vpcsum_l2_forward_async")
 }
 
+int vpcsum_tcp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_src, uint64_t src_len,
+                           const vpcsum_tcphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* d_seg, uint32_t n,
+                           uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_dst) return fail("vpcsum_tcp_build_async: NULL destination arena");
+        if (!d_src && src_len) return fail("vpcsum_tcp_build_async: NULL source arena");
+        if (!d_hdr && n_hdr) return fail("vpcsum_tcp_build_async: NULL templates");
+        if (!d_seg) return fail("vpcsum_tcp_build_async: NULL records");
+        if (!d_frame_len) return fail("vpcsum_tcp_build_async: NULL frame lengths");
+        if ((uintptr_t)d_seg & 7) return fail("vpcsum_tcp_build_async: records not 8-byte aligned");
+        if ((uintptr_t)d_hdr & 3) return fail("vpcsum_tcp_build_async: templates not 4-byte aligned");
+        if ((uintptr_t)d_frame_len & 3) return fail("vpcsum_tcp_build_async: frame lengths not 4-byte aligned");
+        if ((uintptr_t)d_out & 3) return fail("vpcsum_tcp_build_async: out words not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_tcp_build_async: %u records > 2^28", n);
+        VPC_CHECK(launch_tcp_build(d_dst, dst_len, d_src, src_len, d_hdr, n_hdr, d_seg, n, d_frame_len, d_out, d_status,
+                                   (hipStream_t)stream),
+                  "TCP build launch");
+        return 0;
+    } VPC_CATCH("vpcsum_tcp_build_async")
+}
+
 int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream) {
     try {
         if (!f || !n_out) return fail("vpcsum_flowtab_collect: NULL table or count");
@@ -1869,6 +1900,76 @@ int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uin
         return ctx_nat_flow_frames(c, f, h_arena, arena_len, h_frame_off, h_frame_len, n, h_status, h_verdict, h_port, true,
                                    nat_mode, ticket, "vpcsum_ctx_nat_flow_forward_frames");
     } VPC_CATCH("vpcsum_ctx_nat_flow_forward_frames")
+}
+
+// The TCP segment build of host memory: frames written in place into a registered destination, the
+// payloads read in place from a registered source or staged as one span.  Always launched (the
+// service grid has no build), on the slot's one stream.
+int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
+                                const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* h_seg, uint32_t n,
+                                uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
+    const char* what = "vpcsum_ctx_build_tcp_frames";
+    try {
+        if (!c || !ticket) return fail("%s: NULL context or ticket", what);
+        if (n > c->max_pkts) return fail("%s: %u records > capacity %u", what, n, c->max_pkts);
+        if (n_hdr > c->max_pkts) return fail("%s: %u templates > capacity %u", what, n_hdr, c->max_pkts);
+        if (n && (!h_dst || !h_seg || !h_frame_len || (!h_hdr && n_hdr) || (!h_src && src_len)))
+            return fail("%s: NULL destination, source, templates, records or frame lengths", what);
+        std::lock_guard<std::mutex> lk(c->mu);
+        VPC_ON_DEVICE(c->device);
+        uint8_t* base = n ? mapped_dev(c, h_dst, dst_len) : nullptr;
+        if (n && !base) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
+        // the source: read in place when registered, else the span of the payloads that lie inside it
+        const uint8_t* src_dev = n && src_len ? mapped_dev(c, h_src, src_len) : nullptr;
+        const bool staged = n && src_len && !src_dev;
+        uint64_t lo = UINT64_MAX, hi = 0;
+        if (staged) {
+            for (uint32_t i = 0; i < n; ++i) {
+                const vpcsum_tcpseg_t& r = h_seg[i];
+                if (!r.data_len || r.data_off > src_len || r.data_len > src_len - r.data_off) continue;
+                lo = std::min(lo, r.data_off);
+                hi = std::max(hi, r.data_off + r.data_len);
+            }
+            if (hi > lo && hi - lo > c->max_arena)
+                return fail("%s: the payloads span %llu bytes > capacity %llu", what, (unsigned long long)(hi - lo),
+                            (unsigned long long)c->max_arena);
+        }
+        const uint64_t span = hi > lo ? hi - lo : 0;
+        Batch b;
+        Slot* slot = slot_acquire(c, &b.ticket);
+        if (!slot) return -1;
+        Slot& s = *slot;
+        b.n = n;
+        b.zero_copy = true;   // the frames are written in place through the destination's mapping
+        b.user_out = h_out;
+        b.user_status = h_status;
+        b.user_flen = n ? h_frame_len : nullptr;
+        if (n) {
+            // records, templates and frame lengths: pinned, sized from max_pkts with the context's first build
+            if (!s.h_tseg.p) VPC_CHECK(s.h_tseg.alloc((size_t)c->max_pkts * sizeof(vpcsum_tcpseg_t)), what);
+            if (!s.h_thdr.p) VPC_CHECK(s.h_thdr.alloc((size_t)c->max_pkts * sizeof(vpcsum_tcphdr_t)), what);
+            if (!s.h_tlen.p) VPC_CHECK(s.h_tlen.alloc((size_t)c->max_pkts * 4), what);
+            memcpy(s.h_tseg.p, h_seg, (size_t)n * sizeof(vpcsum_tcpseg_t));
+            if (n_hdr) memcpy(s.h_thdr.p, h_hdr, (size_t)n_hdr * sizeof(vpcsum_tcphdr_t));
+            if (staged) {
+                // the library's copy of the records names the staged span; a payload outside the
+                // source stays outside (refused by the kernel), an empty one reads nothing
+                for (uint32_t i = 0; i < n; ++i) {
+                    vpcsum_tcpseg_t& r = s.h_tseg.p[i];
+                    if (r.data_off > src_len || r.data_len > src_len - r.data_off) r.data_off = UINT64_MAX;
+                    else r.data_off = r.data_len ? r.data_off - lo : 0;
+                }
+                if (span) {
+                    memcpy(s.h_arena, h_src + lo, span);   // pageable -> pinned staging
+                    VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, span, hipMemcpyHostToDevice, s.stream), "H2D payloads");
+                }
+            }
+            VPC_CHECK(launch_tcp_build(base, dst_len, staged ? s.d_arena : src_dev, staged ? span : src_len, s.h_thdr.dev, n_hdr,
+                                       s.h_tseg.dev, n, s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
+                      "TCP build launch");
+        }
+        return slot_commit(s, b, ticket);
+    } VPC_CATCH("vpcsum_ctx_build_tcp_frames")
 }
 
 int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint32_t copy_bytes,
@@ -2524,6 +2625,18 @@ int Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames(PNIEnv_vpcsum_long* env, i
                                                   (uint8_t*)arena, (uint64_t)arenaLen, (const uint64_t*)frameOff,
                                                   (const uint32_t*)frameLen, (uint32_t)n, (uint8_t*)status, (uint8_t*)verdict,
                                                   (uint32_t*)port, (uint32_t)natMode, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
+                                                int64_t srcLen, void* hdr, int32_t nHdr, void* seg, int32_t n,
+                                                void* frameLen, void* out, void* status) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames", n < 0 || nHdr < 0 || dstLen < 0 || srcLen < 0,
+                         "buildTcpFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_build_tcp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)dst, (uint64_t)dstLen, (const uint8_t*)src,
+                                           (uint64_t)srcLen, (const vpcsum_tcphdr_t*)hdr, (uint32_t)nHdr,
+                                           (const vpcsum_tcpseg_t*)seg, (uint32_t)n, (uint32_t*)frameLen, (uint32_t*)out,
+                                           (uint8_t*)status, t);
     });
 }
 

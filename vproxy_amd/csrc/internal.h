@@ -108,6 +108,13 @@ hipError_t launch_l2_forward(uint8_t* arena, uint64_t arena_len, const uint64_t*
                              const uint8_t* verdict, const uint8_t* status, const vpcsum_fastpath_t* fp, uint32_t n,
                              uint32_t* port_out, hipStream_t stream);
 
+// TCP segment build (tcp_build.hip k_tcp_build, vpcsum.h vpcsum_tcp_build_async's rule): frame i from
+// template hdrs[segs[i].hdr] and the payload at src + segs[i].data_off, written at dst +
+// segs[i].frame_off; frame_len_out[i] = L or 0 for a refused record; out / status may be NULL
+hipError_t launch_tcp_build(uint8_t* dst, uint64_t dst_len, const uint8_t* src, uint64_t src_len,
+                            const vpcsum_tcphdr_t* hdrs, uint32_t n_hdr, const vpcsum_tcpseg_t* segs, uint32_t n,
+                            uint32_t* frame_len_out, uint32_t* out, uint8_t* status, hipStream_t stream);
+
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t grid, hipStream_t stream);
 hipError_t launch_pattern_probe(const uint8_t* arena, uint64_t arena_len, const void* desc, uint32_t n, uint32_t* sink,
                                 uint32_t grid, hipStream_t stream);

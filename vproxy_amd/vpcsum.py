@@ -50,6 +50,16 @@ FLOW_DTYPE = np.dtype([("key", TUPLE_DTYPE), ("rw", NAT_DTYPE), ("cookie", "<u8"
 FLOW_MISS, FLOW_HIT, FLOW_PUNT = 0, 1, 2
 # vpcsum_fastpath_t: a flow's Ethernet addresses (wire order) and output port; port 0 = no Fastpath
 FASTPATH_DTYPE = np.dtype([("dst", "u1", 6), ("src", "u1", 6), ("port", "<u4")])
+# vpcsum_tcphdr_t (64 B): one connection direction's header template for the TCP segment build --
+# Ethernet addresses, l2_len 14 / 0, version, tos, ttl, addresses, and the wire bytes of ports,
+# ack, window, IPv4 identification and flags | fragment offset
+TCPHDR_DTYPE = np.dtype([("eth_dst", "u1", 6), ("eth_src", "u1", 6), ("l2_len", "u1"), ("l3_ver", "u1"), ("tos", "u1"),
+                         ("ttl", "u1"), ("src", "u1", 16), ("dst", "u1", 16), ("sport", "u1", 2), ("dport", "u1", 2),
+                         ("ack", "u1", 4), ("window", "u1", 2), ("ident", "u1", 2), ("frag", "u1", 2), ("rsv", "u1", 2)])
+# vpcsum_tcpseg_t (32 B): one frame to build -- where it goes, where its payload lies, seq (host
+# order), template index, the room at frame_off, payload length, TCP flags
+TCPSEG_DTYPE = np.dtype([("frame_off", "<u8"), ("data_off", "<u8"), ("seq", "<u4"), ("hdr", "<u4"), ("frame_cap", "<u4"),
+                         ("data_len", "<u2"), ("flags", "u1"), ("rsv", "u1")])
 
 # Every symbol include/vpcsum.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -84,6 +94,7 @@ EXPORTS = [
     "vpcsum_flowtab_set_fastpath", "vpcsum_flow_lookup_fp_async", "vpcsum_l2_forward_async",
     "vpcsum_ctx_nat_flow_forward_frames", "Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath",
     "Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames",
+    "vpcsum_tcp_build_async", "vpcsum_ctx_build_tcp_frames", "Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames",
 ]
 
 
@@ -260,6 +271,8 @@ def _declare(L):
         "vpcsum_flow_lookup_fp_async": ([P, P, U32, P, P, P, P], I),
         "vpcsum_l2_forward_async": ([P, U64, P, P, P, P, P, U32, P, P], I),
         "vpcsum_ctx_nat_flow_forward_frames": ([P, P, P, U64, P, P, U32, P, P, P, U32, P], I),
+        "vpcsum_tcp_build_async": ([P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
+        "vpcsum_ctx_build_tcp_frames": ([P, P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -507,6 +520,21 @@ def l2_forward(arena, frame_off, frame_len, verdict, status, fastpath, n: int, p
     _check(lib().vpcsum_l2_forward_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(frame_off), _ptr(frame_len),
                                          _ptr(verdict), _ptr(status), _ptr(fastpath), n, _ptr(port), _stream(stream)),
            "vpcsum_l2_forward_async")
+
+
+def tcp_build(dst, src, hdrs, n_hdr: int, segs, n: int, frame_len, out=None, status=None, stream=None):
+    """vpcsum_tcp_build_async on device tensors: `dst` / `src` uint8 arenas, `hdrs` n_hdr x 64 bytes
+    (TCPHDR_DTYPE), `segs` n x 32 bytes (TCPSEG_DTYPE), `frame_len` n x uint32 (written: L, or 0 for a
+    refused record), `out` n x uint32 and `status` n bytes (each may be None).  Frame i is built at
+    dst + frame_off from its template and the payload at src + data_off, sums included."""
+    assert hdrs.numel() * hdrs.element_size() >= n_hdr * TCPHDR_DTYPE.itemsize
+    assert segs.numel() * segs.element_size() >= n * TCPSEG_DTYPE.itemsize
+    assert frame_len.numel() * frame_len.element_size() >= n * 4
+    assert out is None or out.numel() * out.element_size() >= n * 4
+    assert status is None or status.numel() >= n
+    _check(lib().vpcsum_tcp_build_async(_ptr(dst), dst.numel() * dst.element_size(), _ptr(src),
+                                        src.numel() * src.element_size(), _ptr(hdrs), n_hdr, _ptr(segs), n, _ptr(frame_len),
+                                        _ptr(out), _ptr(status), _stream(stream)), "vpcsum_tcp_build_async")
 
 
 class FlowTable:
@@ -765,6 +793,28 @@ class Context:
                "vpcsum_ctx_nat_flow_forward_frames")
         self.wait(t.value)
         return status, verdict, port
+
+    def build_tcp_frames(self, dst: np.ndarray, src: np.ndarray, hdrs: np.ndarray, segs: np.ndarray, want_out: bool = True,
+                         want_status: bool = True):
+        """vpcsum_ctx_build_tcp_frames: the frames of `segs` (TCPSEG_DTYPE) built from `hdrs`
+        (TCPHDR_DTYPE) and the payloads in `src` into `dst`, which must lie in a registered arena;
+        a registered `src` is read in place, any other staged.  Returns (frame_len, out, status) per
+        record (out / status None when not asked for); frame_len 0: the record was refused."""
+        assert hdrs.dtype == TCPHDR_DTYPE and segs.dtype == TCPSEG_DTYPE
+        n, n_hdr = len(segs), len(hdrs)
+        hd, sg = np.ascontiguousarray(hdrs), np.ascontiguousarray(segs)
+        frame_len = np.zeros(n, np.uint32)
+        out = np.zeros(n, np.uint32) if want_out else None
+        status = np.zeros(n, np.uint8) if want_status else None
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_build_tcp_frames(self.h, dst.ctypes.data, dst.nbytes, src.ctypes.data if src.nbytes else None,
+                                                 src.nbytes, hd.ctypes.data if n_hdr else None, n_hdr,
+                                                 sg.ctypes.data if n else None, n, frame_len.ctypes.data,
+                                                 None if out is None else out.ctypes.data,
+                                                 None if status is None else status.ctypes.data, ctypes.byref(t)),
+               "vpcsum_ctx_build_tcp_frames")
+        self.wait(t.value)
+        return frame_len, out, status
 
     def set_service(self, idle_us: int):
         """Low-latency flushes from registered arenas (persistent service grid); 0 = off."""
