@@ -221,7 +221,87 @@ static void test_header_extents() {
     CHECK(pre_staged_len(arena.get(), udp, pre4, VPCSUM_PRE_FMT_PRE4, &cut) == 32 && cut);
 }
 
+// An exact-size copy of a byte list: reading or writing past it is a sanitizer error
+static std::unique_ptr<uint8_t[]> exact_bytes(const std::vector<uint8_t>& v) {
+    std::unique_ptr<uint8_t[]> p(new uint8_t[v.size()]);
+    memcpy(p.get(), v.data(), v.size());
+    return p;
+}
+
+static void test_place_checksums() {
+    // seven packets in a 200-byte arena filled with 0xEE; out word 0xAABBCCDD: L4 sum AA BB, IP sum CC DD
+    const uint64_t arena_len = 200;
+    std::vector<uint8_t> before(arena_len, 0xEE);
+    const uint8_t BAD = VPCSUM_S_BAD_DESC, OK = VPCSUM_S_DONE;
+    std::unique_ptr<vpcsum_desc_t[]> d(new vpcsum_desc_t[7]);
+    std::unique_ptr<uint32_t[]> out(new uint32_t[7]);
+    std::unique_ptr<uint8_t[]> st(new uint8_t[7]);
+    d[0] = mk(0, 20, 20, 4, 6, VPCSUM_F_IP | VPCSUM_F_L4);    // refused, first: untouched
+    d[1] = mk(20, 20, 20, 4, 6, VPCSUM_F_IP);                 // IP only
+    d[2] = mk(40, 28, 20, 4, 17, VPCSUM_F_L4);                // L4 only (UDP: field at L4 + 6)
+    d[3] = mk(70, 40, 20, 4, 6, VPCSUM_F_IP | VPCSUM_F_L4);   // both (TCP: field at L4 + 16)
+    d[4] = mk(110, 44, 40, 6, 58, VPCSUM_F_L4P);              // F_L4P (ICMPv6: field at L4 + 2)
+    d[5] = mk(156, 24, 20, 4, 47, VPCSUM_F_IP | VPCSUM_F_L4); // no checksum field in the protocol: IP only
+    d[6] = mk(180, 20, 0, 4, 1, VPCSUM_F_IP | VPCSUM_F_L4);   // refused, last (ends at the arena's end): untouched
+    for (int i = 0; i < 7; ++i) { out[i] = 0xAABBCCDDu + 0x01010101u * (uint32_t)i; st[i] = OK; }
+    st[0] = BAD;
+    st[6] = BAD | OK;
+    std::vector<uint8_t> want = before;
+    want[20 + 10] = 0xCD; want[20 + 11] = 0xDE;                                   // out[1] = AB BC CD DE
+    want[40 + 20 + 6] = 0xAC; want[40 + 20 + 7] = 0xBD;                           // out[2] = AC BD CE DF
+    want[70 + 10] = 0xCF; want[70 + 11] = 0xE0; want[70 + 36] = 0xAD; want[70 + 37] = 0xBE;   // out[3] = AD BE CF E0
+    want[110 + 42] = 0xAE; want[110 + 43] = 0xBF;                                 // out[4] = AE BF D0 E1
+    want[156 + 10] = 0xD1; want[156 + 11] = 0xE2;                                 // out[5] = AF C0 D1 E2
+    std::unique_ptr<uint8_t[]> arena = exact_bytes(before);
+    place_checksums(arena.get(), d.get(), out.get(), st.get(), 7);
+    CHECK(memcmp(arena.get(), want.data(), arena_len) == 0);
+    // a refused packet's descriptor is not trusted: one far outside the arena is skipped, first and last
+    d[0] = mk(UINT64_MAX - 5, 20, 20, 4, 6, VPCSUM_F_IP | VPCSUM_F_L4);
+    d[6] = mk(1ull << 40, 20, 65000, 4, 6, VPCSUM_F_IP | VPCSUM_F_L4);
+    arena = exact_bytes(before);
+    place_checksums(arena.get(), d.get(), out.get(), st.get(), 7);
+    CHECK(memcmp(arena.get(), want.data(), arena_len) == 0);
+    place_checksums(nullptr, nullptr, nullptr, nullptr, 0);   // an empty batch touches nothing
+}
+
+static void test_return_nat_headers() {
+    // the caller's arena: 0x11 everywhere; the staging (gather_blocks' layout): byte k holds 0x80 + k
+    const uint64_t arena_len = 300;
+    std::vector<uint8_t> before(arena_len, 0x11), stage_v(160);
+    for (size_t k = 0; k < stage_v.size(); ++k) stage_v[k] = (uint8_t)(0x80 + k);
+    std::unique_ptr<vpcsum_desc_t[]> d(new vpcsum_desc_t[4]), sd(new vpcsum_desc_t[4]);
+    std::unique_ptr<uint8_t[]> st(new uint8_t[4]);
+    d[0] = mk(5, 100, 20, 4, 6);      // IPv4 / TCP, 80-B segment: 38 B back, 80 B (L4 + 60) with the TCP rewrites
+    d[1] = mk(120, 40, 20, 4, 17);    // IPv4 / UDP: 28 B back either way
+    d[2] = mk(170, 50, 20, 4, 6);     // refused: neither read nor written
+    d[3] = mk(250, 50, 20, 4, 6);     // IPv4 / TCP ending at the arena's end, 30-B segment: 38 B, or all 50
+    for (int i = 0; i < 4; ++i) { sd[i] = d[i]; st[i] = VPCSUM_S_DONE; }
+    sd[0].l3_off = 5;      // staged [0, 112): needs stage[5, 85)
+    sd[1].l3_off = 112 + 8;   // needs stage[120, 148)
+    sd[2].l3_off = UINT64_MAX;
+    sd[3].l3_off = 10;     // (the test's own layout: overlaps packet 0's blocks, the copy is what is checked) stage[10, 60)
+    st[2] = VPCSUM_S_BAD_DESC;
+    for (int tcp = 0; tcp < 2; ++tcp) {
+        std::vector<uint8_t> want = before;
+        const uint32_t len0 = tcp ? 80 : 38, len3 = tcp ? 50 : 38;
+        for (uint32_t k = 0; k < len0; ++k) want[5 + k] = (uint8_t)(0x80 + 5 + k);
+        for (uint32_t k = 0; k < 28; ++k) want[120 + k] = (uint8_t)(0x80 + 120 + k);
+        for (uint32_t k = 0; k < len3; ++k) want[250 + k] = (uint8_t)(0x80 + 10 + k);
+        std::unique_ptr<uint8_t[]> arena = exact_bytes(before);
+        // the staging at the exact size the copies need: through byte 148 (packet 1's 28 B)
+        stage_v.resize(148);
+        const std::unique_ptr<uint8_t[]> stage = exact_bytes(stage_v);
+        return_nat_headers(arena.get(), d.get(), stage.get(), sd.get(), st.get(), 4, tcp != 0);
+        CHECK(memcmp(arena.get(), want.data(), arena_len) == 0);
+    }
+    CHECK(nat_tcp_header_end(d[0]) == 80 && nat_tcp_header_end(d[1]) == 28 && nat_tcp_header_end(d[3]) == 50);
+    CHECK(nat_tcp_header_end(mk(0, 39, 20, 4, 6)) == 38);   // 19 B of TCP header: no TCP rewrite ran, the plain extent
+    return_nat_headers(nullptr, nullptr, nullptr, nullptr, nullptr, 0, true);
+}
+
 int main() {
+    test_place_checksums();
+    test_return_nat_headers();
     test_span();
     test_l4_field();
     test_gather_random();

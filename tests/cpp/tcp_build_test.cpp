@@ -171,6 +171,59 @@ static void check_refusals() {
     CHECK(!fits(v4, {0, top, 54, 0}, big, top - 1) && fits(v4, {0, top, 54, 0}, big, top));
 }
 
+// The payload span of a staged source and the records rebased to it, over an exact-size copy of the
+// records; `want`: the data_off each record must have afterwards.
+struct Pay {
+    uint64_t data_off;
+    uint16_t data_len;
+};
+static void span_is(const std::vector<Pay>& recs, uint64_t src_len, uint64_t capacity, bool fits, uint64_t lo, uint64_t len,
+                    const std::vector<uint64_t>& want) {
+    std::unique_ptr<vpcsum_tcpseg_t[]> seg(new vpcsum_tcpseg_t[recs.size()]);
+    for (size_t i = 0; i < recs.size(); ++i) {
+        memset(&seg[i], 0, sizeof(seg[i]));
+        seg[i].frame_off = 1000 * i;
+        seg[i].seq = 7;
+        seg[i].data_off = recs[i].data_off;
+        seg[i].data_len = recs[i].data_len;
+    }
+    TcpPayloadSpan sp = {99, 99};
+    CHECK(tcp_build_payload_span(seg.get(), (uint32_t)recs.size(), src_len, capacity, &sp) == fits);
+    CHECK(sp.lo == lo && sp.len == len);
+    tcp_build_rebase_payloads(seg.get(), (uint32_t)recs.size(), src_len, sp.lo);
+    for (size_t i = 0; i < recs.size(); ++i) {
+        CHECK(seg[i].data_off == want[i]);
+        CHECK(seg[i].data_len == recs[i].data_len && seg[i].frame_off == 1000 * i && seg[i].seq == 7);   // nothing else moves
+    }
+}
+
+static void check_payload_span() {
+    const uint64_t top = ~0ull, big = 1ull << 40, out = UINT64_MAX;
+    span_is({}, 1000, big, true, 0, 0, {});
+    span_is({{300, 50}}, 1000, big, true, 300, 50, {0});                        // a single record
+    span_is({{300, 0}}, 1000, big, true, 0, 0, {0});                            // data_len == 0: reads nothing
+    span_is({{1000, 0}}, 1000, big, true, 0, 0, {0});                           // data_off == src_len, empty: accepted
+    span_is({{1000, 1}}, 1000, big, true, 0, 0, {out});                         // data_off == src_len, one byte: outside
+    span_is({{1001, 0}}, 1000, big, true, 0, 0, {out});                         // data_off > src_len: outside even when empty
+    span_is({{990, 11}}, 1000, big, true, 0, 0, {out});                         // one byte past the end
+    span_is({{990, 10}}, 1000, big, true, 990, 10, {0});                        // ends exactly at src_len
+    // data_off + data_len wraps past 2^64 to a small number: refused, and no part of the span
+    span_is({{top - 4, 10}, {100, 20}}, 1000, big, true, 100, 20, {out, 0});
+    span_is({{top, 1}}, top, big, true, 0, 0, {out});
+    span_is({{top - 4, 10}, {top - 4, 4}}, top, big, true, top - 4, 4, {out, 0});   // inside the source, 10 > the 4 bytes left
+    span_is({{top - 10, 10}}, top, big, true, top - 10, 10, {0});               // ends exactly at src_len = 2^64 - 1
+    // several: the span is over the accepted, non-empty ones; empty and refused ones do not widen it
+    span_is({{500, 100}, {5, 0}, {200, 50}, {2000, 8}, {950, 50}, {999, 2}}, 1000, big, true, 200, 800,
+            {300, 0, 0, out, 750, out});
+    span_is({{2000, 8}, {1000, 1}, {top, 65535}}, 1000, big, true, 0, 0, {out, out, out});   // all refused: span 0
+    span_is({{2000, 8}}, 1000, 0, true, 0, 0, {out});                           // span 0 fits a capacity of 0
+    // the staging's room: exactly at capacity, one byte over (the span is still reported)
+    span_is({{100, 60}, {300, 100}}, 1000, 300, true, 100, 300, {0, 200});
+    span_is({{100, 60}, {300, 100}}, 1000, 299, false, 100, 300, {0, 200});
+    span_is({{0, 1}}, 1, 1, true, 0, 1, {0});
+    span_is({{0, 1}}, 1, 0, false, 0, 1, {0});
+}
+
 static std::vector<uint8_t> unhex(const char* s) {
     std::vector<uint8_t> b;
     const size_t n = strlen(s);
@@ -225,6 +278,7 @@ int main(int argc, char** argv) {
     for (int ver : {4, 6})
         for (int l2 : {0, 14}) check_layout(ver, l2);
     check_refusals();
+    check_payload_span();
     if (argc == 4) check_reference(argv[1], (uint32_t)strtoul(argv[2], nullptr, 0), (uint32_t)strtoul(argv[3], nullptr, 0));
     if (g_fail) return 1;
     printf("tcp_build ok%s\n", argc == 4 ? " (with the reference frame)" : "");

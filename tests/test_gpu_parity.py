@@ -1384,7 +1384,7 @@ def test_unregister_with_batch_in_flight(V, orc, service):
     ctx.close()
 
 
-def _batch_kinds_inputs(orc, n):
+def _batch_kinds_inputs(V, orc, n):
     """One batch of every kind the context takes, n packets each: Ethernet frames for a registered
     arena, and pageable arenas with descriptors (one of them outside its arena) for NAT, a
     MODE_WRITE submit and a pre-image submit."""
@@ -1406,23 +1406,61 @@ def _batch_kinds_inputs(orc, n):
                pre_arena=pre_arena, pre_desc=pre_desc.copy(), pre=pre)
     for k, arena in (("r_desc", "R"), ("nat_desc", "nat_arena"), ("wr_desc", "wr_arena"), ("pre_desc", "pre_arena")):
         inp[k]["l3_off"][n // 2] = inp[arena].nbytes + 1
+    # the flow batches: a table (at most 64 flows) keyed by the tuples of about half the picked
+    # TCP / UDP frames -- those a lookup can HIT (no SYN / FIN / RST) first, so that at least one is
+    # among them -- and a Fastpath on every other flow, the first included
+    from test_gpu_flow import changed, mk_entry, mk_flows, tuples_of
+    frng = np.random.default_rng(2000 + n)
+    tu = tuples_of(V, [fs[i]["frame"] for i in pick])
+    keyed = [t for t in tu if int(t["l3_ver"]) in (4, 6) and int(t["l4_proto"]) in (6, 17)]
+    keyed.sort(key=lambda t: int(t["l4_proto"]) == 6 and bool(int(t["tcp_flags"]) & 0x07))   # stable: HIT-able first
+    keys = {changed(V, t, tcp_flags=0).tobytes(): changed(V, t, tcp_flags=0) for t in keyed[::2]}
+    keys = list(keys.values())
+    assert 0 < len(keys) <= 64
+    inp["flows"] = mk_flows(V, keys, [mk_entry(V, frng, mask=0x0f) for _ in keys], range(1, len(keys) + 1))
+    inp["fp_keys"] = np.array(keys[::2], V.TUPLE_DTYPE)
+    inp["fps"] = np.zeros(len(inp["fp_keys"]), V.FASTPATH_DTYPE)
+    inp["fps"].view(np.uint8)[:] = frng.integers(0, 256, inp["fps"].nbytes, dtype=np.uint8)
+    inp["fps"]["port"] = np.arange(7, 7 + len(inp["fps"]))
+    # the build batch: n records into 2048-B chunks of a destination of its own, payloads from a
+    # pageable source (so their span is staged); record 1 has no payload, record n // 2 lies outside the source
+    inp["b_src"] = frng.integers(0, 256, 60000, dtype=np.uint8)
+    hd = np.zeros(2, V.TCPHDR_DTYPE)
+    hd.view(np.uint8)[:] = frng.integers(0, 256, hd.nbytes, dtype=np.uint8)
+    hd["l2_len"], hd["l3_ver"], hd["rsv"] = (14, 0), (4, 6), 0
+    sg = np.zeros(n, V.TCPSEG_DTYPE)
+    sg["frame_off"], sg["frame_cap"], sg["hdr"], sg["flags"] = np.arange(n) * 2048, 2048, np.arange(n) % 2, 0x18
+    sg["seq"] = frng.integers(0, 1 << 32, n, dtype=np.uint64)
+    sg["data_len"] = frng.integers(1, 1401, n)
+    sg["data_off"] = frng.integers(0, inp["b_src"].nbytes - 1400, n)
+    sg["data_len"][1] = 0
+    sg["data_off"][n // 2] = inp["b_src"].nbytes + 1
+    inp.update(b_hdr=hd, b_seg=sg, b_dst=np.zeros(n * 2048, np.uint8))
     return inp
 
 
 def _run_batch_kinds(V, inp, service, waited):
-    """The six submits of test_slots_carry_nothing_between_batch_kinds on a context of their own;
+    """The nine submits of test_slots_carry_nothing_between_batch_kinds on a context of their own;
     waited: each one waited at once.  Returns every result array and every arena."""
     import ctypes
     L, n = V.lib(), inp["n"]
-    a = {k: inp[k].copy() for k in ("R", "nat_arena", "wr_arena", "pre_arena")}
+    a = {k: inp[k].copy() for k in ("R", "nat_arena", "wr_arena", "pre_arena", "b_dst")}
+    a["F"], a["FF"] = inp["R"].copy(), inp["R"].copy()   # the flow batches rewrite the frames in place
     r = dict(nat_st=np.zeros(n, np.uint8), wr_out=np.zeros(n, np.uint32), wr_st=np.zeros(n, np.uint8),
              p_desc=np.zeros(n, V.DESC_DTYPE), p_st=np.zeros(n, np.uint8), p_tu=np.zeros(n, V.TUPLE_DTYPE),
              h_st=np.zeros(n, np.uint8), h_hs=np.zeros(n, V.HSUM_DTYPE), pre_out=np.zeros(n, np.uint32),
-             pre_st=np.zeros(n, np.uint8), v_out=np.zeros(n, np.uint32), v_st=np.zeros(n, np.uint8))
+             pre_st=np.zeros(n, np.uint8), v_out=np.zeros(n, np.uint32), v_st=np.zeros(n, np.uint8),
+             f_st=np.zeros(n, np.uint8), f_vd=np.zeros(n, np.uint8), ff_st=np.zeros(n, np.uint8), ff_vd=np.zeros(n, np.uint8),
+             ff_port=np.zeros(n, np.uint32), b_len=np.zeros(n, np.uint32), b_out=np.zeros(n, np.uint32),
+             b_st=np.zeros(n, np.uint8))
     ctx = V.Context(0, max_arena=1 << 20, max_pkts=64)
-    ctx.register(a["R"])
+    for k in ("R", "F", "FF", "b_dst"):
+        ctx.register(a[k])
     if service:
         ctx.set_service(service)
+    tab = V.FlowTable(64)
+    tab.update(add=inp["flows"])
+    assert tab.set_fastpath(inp["fp_keys"], inp["fps"]) == 0
     tickets = []
 
     def step(t):
@@ -1430,22 +1468,39 @@ def _run_batch_kinds(V, inp, service, waited):
         if waited:
             ctx.wait(t)
 
-    def frames_call(fn, *results):
+    def frames_call(fn, *results, arena="R", tab=None, nat_mode=None):
         t = ctypes.c_uint64()
-        rc = fn(ctx.h, a["R"].ctypes.data, a["R"].nbytes, inp["fo"].ctypes.data, inp["fl"].ctypes.data, n,
-                *[None if x is None else x.ctypes.data for x in results], ctypes.byref(t))
+        rc = fn(ctx.h, *([] if tab is None else [tab.h]), a[arena].ctypes.data, a[arena].nbytes, inp["fo"].ctypes.data,
+                inp["fl"].ctypes.data, n, *[None if x is None else x.ctypes.data for x in results],
+                *([] if nat_mode is None else [nat_mode]), ctypes.byref(t))
         assert rc == 0, L.vpcsum_last_error()
         step(t.value)
 
+    def build_call():
+        t = ctypes.c_uint64()
+        rc = L.vpcsum_ctx_build_tcp_frames(ctx.h, a["b_dst"].ctypes.data, a["b_dst"].nbytes, inp["b_src"].ctypes.data,
+                                           inp["b_src"].nbytes, inp["b_hdr"].ctypes.data, len(inp["b_hdr"]),
+                                           inp["b_seg"].ctypes.data, n, r["b_len"].ctypes.data, r["b_out"].ctypes.data,
+                                           r["b_st"].ctypes.data, ctypes.byref(t))
+        assert rc == 0, L.vpcsum_last_error()
+        step(t.value)
+
+    # slot 1, slot 0, slot 1, ...: each batch takes the slot of the one two lines above it
     step(ctx.nat_submit(a["nat_arena"], inp["nat_desc"], inp["nat_rw"], r["nat_st"], V.NAT_STRICT_JAVA))
     step(ctx.submit(a["wr_arena"], inp["wr_desc"], r["wr_out"], r["wr_st"], O.MODE_WRITE))
-    frames_call(L.vpcsum_ctx_parse_frames, r["p_desc"], r["p_st"], r["p_tu"])     # finishes the NAT batch
-    frames_call(L.vpcsum_ctx_verify_frames_hsum, None, r["h_st"], r["h_hs"])      # finishes the write-back
+    frames_call(L.vpcsum_ctx_nat_flow_frames, r["f_st"], r["f_vd"], arena="F", tab=tab,
+                nat_mode=V.NAT_RFC1624)                                            # finishes the staged NAT batch
+    build_call()                                                                  # finishes the staged write-back
+    frames_call(L.vpcsum_ctx_parse_frames, r["p_desc"], r["p_st"], r["p_tu"])     # finishes the flow batch
+    frames_call(L.vpcsum_ctx_verify_frames_hsum, None, r["h_st"], r["h_hs"])      # finishes the build
+    frames_call(L.vpcsum_ctx_nat_flow_forward_frames, r["ff_st"], r["ff_vd"], r["ff_port"], arena="FF", tab=tab,
+                nat_mode=V.NAT_STRICT_JAVA)                                        # finishes the parse
     step(ctx.submit_pre(a["pre_arena"], inp["pre_desc"], inp["pre"], r["pre_out"], r["pre_st"], O.MODE_WRITE))
-    step(ctx.submit(a["R"], inp["r_desc"], r["v_out"], r["v_st"], O.MODE_VERIFY))
+    step(ctx.submit(a["R"], inp["r_desc"], r["v_out"], r["v_st"], O.MODE_VERIFY))   # finishes the forwarding flow batch
     for t in reversed(tickets):   # all but the last two are completed already
         ctx.wait(t)
     ctx.close()
+    tab.close()
     r.update(a)
     return r
 
@@ -1453,15 +1508,17 @@ def _run_batch_kinds(V, inp, service, waited):
 @pytest.mark.parametrize("service", [0, 20000])
 def test_slots_carry_nothing_between_batch_kinds(V, orc, service):
     """Batches of different kinds follow each other on the context's two slots without a wait in
-    between -- NAT (staged, strict Java), submit (staged, MODE_WRITE), parse_frames,
-    verify_frames_hsum, submit_pre (staged), submit (zero-copy verify) -- so that each slot goes
-    from one kind to the next, the staged NAT and MODE_WRITE batches finished by the submit that
-    takes their slot, and the tickets are waited in reverse order.  Every result array and every
-    arena equals what a twin context gives with each call waited at once (each of those forms is
-    pinned to the oracle by the tests of its own): nothing of a slot's previous batch -- service
-    sequence, header-sum, descriptor or tuple destination, write-back -- acts on the next."""
+    between -- NAT (staged, strict Java), submit (staged, MODE_WRITE), nat_flow_frames,
+    build_tcp_frames (pageable source: its payload span staged), parse_frames, verify_frames_hsum,
+    nat_flow_forward_frames, submit_pre (staged), submit (zero-copy verify) -- so that each slot
+    goes from one kind to the next, the staged NAT and MODE_WRITE batches finished by the flow and
+    build batches that take their slots, and the tickets are waited in reverse order.  Every result
+    array and every arena equals what a twin context gives with each call waited at once (each of
+    those forms is pinned to the oracle by the tests of its own): nothing of a slot's previous
+    batch -- service sequence, header-sum, descriptor, tuple, verdict, port or frame-length
+    destination, write-back -- acts on the next."""
     for n in (5, 37):   # above the 3 inline descriptors, below the service grid's 512
-        inp = _batch_kinds_inputs(orc, n)
+        inp = _batch_kinds_inputs(V, orc, n)
         want = _run_batch_kinds(V, inp, service, waited=True)
         got = _run_batch_kinds(V, inp, service, waited=False)
         for k in want:
@@ -1469,6 +1526,10 @@ def test_slots_carry_nothing_between_batch_kinds(V, orc, service):
         assert not np.array_equal(want["nat_arena"], inp["nat_arena"])   # the batches did act
         assert not np.array_equal(want["wr_arena"], inp["wr_arena"])
         assert np.any(want["p_desc"]["l3_len"]) and np.any(want["h_hs"].view(np.uint8)) and np.any(want["v_st"])
+        for vd in (want["f_vd"], want["ff_vd"]):   # the table was consulted: flows found and not found
+            assert np.any(vd == V.FLOW_HIT) and np.any(vd == V.FLOW_MISS)
+        assert not np.array_equal(want["F"], inp["R"]) and not np.array_equal(want["FF"], inp["R"])
+        assert np.any(want["ff_port"]) and np.any(want["b_len"]) and np.any(want["b_dst"])
 
 
 def test_egress_small_flush_hand_back(V, orc):

@@ -105,70 +105,102 @@ int num_cus(int device) {
     return cache[device];
 }
 
+// A buffer that frees itself: Free releases the host pointer p.  Move-only, so that assigning a
+// fresh Slot or Service over a used one frees what the old one held, member by member.
+template <class T, hipError_t (*Free)(void*)>
+struct Owned {
+    T* p = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+        free();   // (a buffer moved onto itself ends up empty)
+        p = o.p;
+        o.p = nullptr;
+        return *this;
+    }
+    ~Owned() { free(); }
+    void free() {
+        if (p) (void)Free(p);
+        p = nullptr;
+    }
+};
+
 // A pinned host buffer the device reads and writes in place (mapped, coherent: uncached on the
 // GPU): the host pointer and its device address as one value.  alloc() pins and maps; the context
 // and the service pin a group of buffers before they map them, with pin() and map().
 template <class T>
-struct Mapped {
-    T* p = nullptr;     // host
-    T* dev = nullptr;   // the same bytes as the device addresses them
-    hipError_t pin(size_t bytes) { return hipHostMalloc((void**)&p, bytes, hipHostMallocMapped | hipHostMallocCoherent); }
-    hipError_t map() { return hipHostGetDevicePointer((void**)&dev, p, 0); }
+struct Mapped : Owned<T, hipHostFree> {
+    T* dev = nullptr;   // the same bytes as the device addresses them (valid while p is)
+    hipError_t pin(size_t bytes) { return hipHostMalloc((void**)&this->p, bytes, hipHostMallocMapped | hipHostMallocCoherent); }
+    hipError_t map() { return hipHostGetDevicePointer((void**)&dev, this->p, 0); }
     hipError_t alloc(size_t bytes) {
         hipError_t e = pin(bytes);
         if (e == hipSuccess) e = map();
-        if (e != hipSuccess) free();
+        if (e != hipSuccess) this->free();
         return e;
-    }
-    void free() {
-        if (p) (void)hipHostFree(p);
-        p = dev = nullptr;
     }
 };
 
+// Its device-only twin: device memory no host code addresses.
+template <class T>
+struct DeviceOnly : Owned<T, hipFree> {
+    hipError_t alloc(size_t bytes) { return hipMalloc((void**)&this->p, bytes); }
+};
+
+// One copy of a finished batch's results into a buffer of the caller's.
+struct HandBack { void* dst; const void* src; size_t bytes; };
+// The most any entry hands back: the status bytes and two more arrays (say descriptors and tuples)
+constexpr size_t kHandBackMax = 3;
+
+// What a staged batch scatters into the caller's frames when it is finished.
+enum class Scatter { None, NatHeaders, CsumFields };
+
 // The batch a slot owns from its submit to the wait (or the later submit) that finishes it.
-enum class BatchKind { Csum, Nat, Parse };
 struct Batch {
-    BatchKind kind = BatchKind::Csum;
+    Scatter scatter = Scatter::None;
     bool zero_copy = false;            // ran on the host frames in place
     uint32_t svc_seq = 0;              // != 0: went to the low-latency service (no event to wait for)
     uint64_t ticket = 0;
     uint32_t n = 0;
     uint32_t mode = 0;
-    uint8_t* user_arena = nullptr;             // staged batch: the frames the results go back into
+    uint8_t* user_arena = nullptr;             // staged batch: the frames the scatter goes back into
     const vpcsum_desc_t* user_desc = nullptr;
-    uint32_t* user_out = nullptr;
-    uint8_t* user_status = nullptr;
-    vpcsum_desc_t* user_desc_out = nullptr;   // parse batch: where descriptors and tuples go
-    vpcsum_tuple_t* user_tuples = nullptr;
-    vpcsum_hsum_t* user_hsum = nullptr;       // verify batch with header sums: where they go
-    uint8_t* user_verdict = nullptr;          // flow batch (vpcsum_ctx_nat_flow_frames): where the verdicts go
-    uint32_t* user_port = nullptr;            // forwarding flow batch: where the output ports go
-    uint32_t* user_flen = nullptr;            // TCP build batch (vpcsum_ctx_build_tcp_frames): where the frame lengths go
+    HandBack back[kHandBackMax] = {};          // the copies slot_finish makes, in this order
+    uint32_t n_back = 0;
+    // The entry lists its results once it knows where they will lie (the slot's staging or the
+    // service's buffers).  A NULL destination -- the caller did not ask -- or an empty array is no copy.
+    template <size_t N>
+    void hand_back(const HandBack (&list)[N]) {
+        static_assert(N <= kHandBackMax, "kHandBackMax: the largest entry's need");
+        for (const HandBack& h : list)
+            if (h.dst && h.bytes) back[n_back++] = h;
+    }
 };
 
 // Per-slot staging of one in-flight batch of a context.
 struct Slot {
-    uint8_t* d_arena = nullptr;
-    vpcsum_desc_t* d_desc = nullptr;
-    uint32_t* d_out = nullptr;
-    uint8_t* d_status = nullptr;
+    DeviceOnly<uint8_t> d_arena;
+    DeviceOnly<vpcsum_desc_t> d_desc;
+    DeviceOnly<uint32_t> d_out;
+    DeviceOnly<uint8_t> d_status;
     Mapped<vpcsum_desc_t> h_desc;      // pinned staging
     Mapped<uint32_t> h_out;
     Mapped<uint8_t> h_status;
-    uint8_t* h_arena = nullptr;        // pinned staging for unregistered arenas (not mapped)
+    Owned<uint8_t, hipHostFree> h_arena;   // pinned staging for unregistered arenas (not mapped)
     Mapped<uint64_t> h_foff;           // received-frame offsets / lengths
     Mapped<uint32_t> h_flen;
-    Mapped<vpcsum_nat_t> h_rw;         // NAT rewrite tables, and their device copy: allocated with the
-    vpcsum_nat_t* d_rw = nullptr;      // context's first NAT batch
-    Mapped<vpcsum_tuple_t> h_tu;       // flow tuples of a parse batch: with the context's first parse batch
-    Mapped<vpcsum_hsum_t> h_hs;        // ingress header sums of a verify batch: with the first such batch
-    vpcsum_tuple_t* d_tu = nullptr;    // a flow batch's tuples (parse -> lookup, device only) and its verdicts:
-    Mapped<uint8_t> h_verdict;         // with the context's first flow batch
-    vpcsum_fastpath_t* d_fp = nullptr; // a forwarding flow batch's Fastpath records (lookup -> L2 write, device only)
-    Mapped<uint32_t> h_port;           // and its output ports: with the context's first such batch
-    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records, templates and frame lengths: with the
-    Mapped<vpcsum_tcphdr_t> h_thdr;    // context's first such batch
+    // Per-packet scratch, max_pkts elements each, allocated by slot_scratch with the context's first
+    // batch that needs it and freed, in this order, when a fresh Slot is assigned over this one:
+    Mapped<vpcsum_nat_t> h_rw;         // per-packet entries (NAT rewrites, pre-images: at most 48 B each)
+    DeviceOnly<vpcsum_nat_t> d_rw;     // and their device copy
+    Mapped<vpcsum_tuple_t> h_tu;       // flow tuples of a parse batch
+    Mapped<vpcsum_hsum_t> h_hs;        // ingress header sums of a verify batch
+    DeviceOnly<vpcsum_tuple_t> d_tu;   // a flow batch's tuples (parse -> lookup)
+    Mapped<uint8_t> h_verdict;         // and its verdicts
+    DeviceOnly<vpcsum_fastpath_t> d_fp;   // a forwarding flow batch's Fastpath records (lookup -> L2 write)
+    Mapped<uint32_t> h_port;           // and its output ports
+    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records, templates and frame lengths
+    Mapped<vpcsum_tcphdr_t> h_thdr;
     Mapped<uint32_t> h_tlen;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
@@ -681,30 +713,11 @@ int vpcsum_stream_sync(void* stream) {
 // Context (host memory) API
 // ------------------------------------------------------------------------------------------
 static void slot_free(Slot& s) {
-    if (s.d_arena) (void)hipFree(s.d_arena);
-    if (s.d_desc) (void)hipFree(s.d_desc);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.d_status) (void)hipFree(s.d_status);
-    s.h_desc.free();
-    s.h_out.free();
-    s.h_status.free();
-    if (s.h_arena) (void)hipHostFree(s.h_arena);
-    s.h_foff.free();
-    s.h_flen.free();
-    s.h_rw.free();
-    if (s.d_rw) (void)hipFree(s.d_rw);
-    s.h_tu.free();
-    s.h_hs.free();
-    if (s.d_tu) (void)hipFree(s.d_tu);
-    s.h_verdict.free();
-    if (s.d_fp) (void)hipFree(s.d_fp);
-    s.h_port.free();
-    s.h_tseg.free();
-    s.h_thdr.free();
-    s.h_tlen.free();
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    s = Slot();
+    const hipEvent_t done = s.done;
+    const hipStream_t stream = s.stream;
+    s = Slot();   // every buffer frees itself, in the order of its declaration, whatever members there are
+    if (done) (void)hipEventDestroy(done);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 static int slot_finish(vpcsum_ctx* c, Slot& s);
@@ -717,12 +730,7 @@ static void svc_free(vpcsum_ctx* c) {
         (void)hipStreamDestroy(v.stream);
     }
     if (v.ctr) (void)hipFree(v.ctr);
-    v.mb.free();
-    v.h_desc.free();
-    v.h_out.free();
-    v.h_status.free();
-    v.h_pre.free();
-    c->svc = Service();
+    c->svc = Service();   // the mailbox and the four buffers free themselves, in that order
 }
 
 int vpcsum_ctx_set_service(vpcsum_ctx_t* c, uint32_t idle_us) {
@@ -789,16 +797,16 @@ int vpcsum_ctx_create(int device, uint64_t max_arena_bytes, uint32_t max_pkts, v
         c->max_pkts = max_pkts;
         for (auto& s : c->slots) {
             hipError_t e = hipSuccess;
-            if ((e = hipMalloc((void**)&s.d_arena, max_arena_bytes + 64)) != hipSuccess ||
-                (e = hipMalloc((void**)&s.d_desc, (size_t)max_pkts * sizeof(vpcsum_desc_t))) != hipSuccess ||
-                (e = hipMalloc((void**)&s.d_out, (size_t)max_pkts * 4)) != hipSuccess ||
-                (e = hipMalloc((void**)&s.d_status, (size_t)max_pkts)) != hipSuccess ||
+            if ((e = s.d_arena.alloc(max_arena_bytes + 64)) != hipSuccess ||
+                (e = s.d_desc.alloc((size_t)max_pkts * sizeof(vpcsum_desc_t))) != hipSuccess ||
+                (e = s.d_out.alloc((size_t)max_pkts * 4)) != hipSuccess ||
+                (e = s.d_status.alloc((size_t)max_pkts)) != hipSuccess ||
                 (e = s.h_desc.pin((size_t)max_pkts * sizeof(vpcsum_desc_t))) != hipSuccess ||
                 (e = s.h_out.pin((size_t)max_pkts * 4)) != hipSuccess ||
                 (e = s.h_status.pin((size_t)max_pkts)) != hipSuccess ||
                 (e = s.h_desc.map()) != hipSuccess || (e = s.h_out.map()) != hipSuccess ||
                 (e = s.h_status.map()) != hipSuccess ||
-                (e = hipHostMalloc((void**)&s.h_arena, max_arena_bytes + 64, 0)) != hipSuccess ||
+                (e = hipHostMalloc((void**)&s.h_arena.p, max_arena_bytes + 64, 0)) != hipSuccess ||
                 (e = s.h_foff.pin((size_t)max_pkts * 8)) != hipSuccess ||
                 (e = s.h_flen.pin((size_t)max_pkts * 4)) != hipSuccess ||
                 (e = s.h_foff.map()) != hipSuccess || (e = s.h_flen.map()) != hipSuccess ||
@@ -898,12 +906,12 @@ static uint8_t* mapped_dev(vpcsum_ctx* c, const uint8_t* p, uint64_t len) {
     return nullptr;
 }
 
-// Whether the staged path may DMA straight from [p, p+len): only when this context registered it
-// (its own registration or its group's), so the page-lock outlives the copy -- vpcsum_ctx_unregister
-// and destroy finish the context's batches before they unpin.  Memory page-locked by anyone else
-// (another context, hipHostMalloc, another library) is copied through the pinned staging first: its
-// owner may unpin or free it while the copy is in flight, which the library cannot see (round 5's
-// version trusted hipPointerGetAttributes here; DESIGN_HISTORY.md "Round 6: the intermittent fault").
+// Whether the library may DMA straight from or to [p, p+len) (vpcsum_ctx_pipeline): only when this
+// context registered it (its own registration or its group's), so the page-lock outlives the copy --
+// vpcsum_ctx_unregister and destroy finish the context's batches before they unpin.  Memory
+// page-locked by anyone else is never a DMA end: its owner may unpin or free it while the copy is
+// in flight, which the library cannot see, so a staged submit copies it through the pinned staging
+// (round 5 trusted hipPointerGetAttributes here; DESIGN_HISTORY.md "Round 6: the intermittent fault").
 static bool is_registered(vpcsum_ctx* c, const uint8_t* p, uint64_t len) { return mapped_dev(c, p, len) != nullptr; }
 
 static uint32_t svc_done(const Service& v) { return __atomic_load_n(&v.mb.p->done, __ATOMIC_ACQUIRE); }
@@ -972,63 +980,19 @@ static int svc_wait(vpcsum_ctx* c, uint32_t seq) {
 static int slot_finish(vpcsum_ctx* c, Slot& s) {
     if (!s.busy) return 0;
     const Batch& b = s.batch;
-    const bool svc = b.svc_seq != 0;   // the results are in the service's buffers
-    if (svc) {
+    if (b.svc_seq) {
         if (svc_wait(c, b.svc_seq) != 0) return -1;
     } else {
         VPC_CHECK(hipEventSynchronize(s.done), "hipEventSynchronize");
     }
-    const uint32_t* res_out = svc ? c->svc.h_out.p : s.h_out.p;
-    const uint8_t* res_status = svc ? c->svc.h_status.p : s.h_status.p;
-    const uint8_t* aux = c->svc.h_pre.p;
-    if (b.user_status) memcpy(b.user_status, res_status, b.n);
-    if (b.user_verdict) memcpy(b.user_verdict, s.h_verdict.p, b.n);
-    if (b.user_port) memcpy(b.user_port, s.h_port.p, (size_t)b.n * 4);
-    if (b.user_flen) memcpy(b.user_flen, s.h_tlen.p, (size_t)b.n * 4);
-    switch (b.kind) {
-    case BatchKind::Nat:
-        // a staged batch's rewritten headers (L3 header through the L4 checksum field; the TCP
-        // header too under VPCSUM_NAT_TCP_REWRITES) go back into the caller's frames; zero-copy
-        // batches rewrote them in place
-        if (!b.zero_copy && b.user_arena) {
-            const bool tcp = (b.mode & VPCSUM_NAT_TCP_REWRITES) != 0;
-            for (uint32_t i = 0; i < b.n; ++i) {
-                if (res_status[i] & VPCSUM_S_BAD_DESC) continue;
-                const vpcsum_desc_t& d = b.user_desc[i];
-                memcpy(b.user_arena + d.l3_off, s.h_arena + s.h_desc.p[i].l3_off,
-                       tcp ? nat_tcp_header_end(d) : nat_header_end(d));
-            }
-        }
-        break;
-    case BatchKind::Parse:   // descriptors and tuples: the pinned staging, or the service's aux buffer
-        if (b.user_desc_out)
-            memcpy(b.user_desc_out, svc ? aux : (const uint8_t*)s.h_desc.p, (size_t)b.n * sizeof(vpcsum_desc_t));
-        if (b.user_tuples)
-            memcpy(b.user_tuples, svc ? aux + (size_t)kSvcBatchMax * sizeof(vpcsum_desc_t) : (const uint8_t*)s.h_tu.p,
-                   (size_t)b.n * sizeof(vpcsum_tuple_t));
-        break;
-    case BatchKind::Csum:
-        if (b.user_out) memcpy(b.user_out, res_out, (size_t)b.n * 4);
-        if (b.user_hsum)   // a verify batch's header sums: the service's aux buffer, or the slot's staging
-            memcpy(b.user_hsum, svc ? (const void*)aux : (const void*)s.h_hs.p, (size_t)b.n * sizeof(vpcsum_hsum_t));
-        if ((b.mode & VPCSUM_MODE_WRITE) && b.user_arena && !b.zero_copy) {
-            // place the GPU results into the caller's frames (big endian, as ByteArray.int16)
-            for (uint32_t i = 0; i < b.n; ++i) {
-                const vpcsum_desc_t& d = b.user_desc[i];
-                if (res_status[i] & VPCSUM_S_BAD_DESC) continue;
-                uint8_t* l3 = b.user_arena + d.l3_off;
-                const uint32_t w = res_out[i];
-                if (d.flags & VPCSUM_F_IP) { l3[10] = (uint8_t)(w >> 8); l3[11] = (uint8_t)w; }
-                if (d.flags & (VPCSUM_F_L4 | VPCSUM_F_L4P)) {
-                    const int fld = l4_field_host(d.l4_proto);
-                    if (fld < 0) continue;   // no L4 sum: the kernel refused the descriptor (BAD above)
-                    l3[d.l4_off + fld] = (uint8_t)(w >> 24);
-                    l3[d.l4_off + fld + 1] = (uint8_t)(w >> 16);
-                }
-            }
-        }
-        break;
-    }
+    for (uint32_t k = 0; k < b.n_back; ++k) memcpy(b.back[k].dst, b.back[k].src, b.back[k].bytes);
+    // a staged batch's results go back into the caller's frames (a zero-copy batch wrote them in
+    // place), by the status bytes of the staging
+    if (b.scatter == Scatter::NatHeaders)
+        return_nat_headers(b.user_arena, b.user_desc, s.h_arena.p, s.h_desc.p, s.h_status.p, b.n,
+                           (b.mode & VPCSUM_NAT_TCP_REWRITES) != 0);
+    else if (b.scatter == Scatter::CsumFields)
+        place_checksums(b.user_arena, b.user_desc, s.h_out.p, s.h_status.p, b.n);
     s.batch = Batch();
     s.busy = false;
     return 0;
@@ -1054,17 +1018,47 @@ static int slot_commit(Slot& s, const Batch& b, uint64_t* ticket) {
     return 0;
 }
 
-// The slot's per-packet entry staging (NAT rewrites, pre-images: at most 48 B each), pinned and
-// mapped plus a device copy, allocated with the context's first batch that carries entries.
-static int slot_rw_alloc(vpcsum_ctx* c, Slot& s, const char* what) {
-    if (s.h_rw.p) return 0;
-    const size_t bytes = (size_t)c->max_pkts * sizeof(vpcsum_nat_t);
-    hipError_t e = s.h_rw.alloc(bytes);
-    if (e == hipSuccess && (e = hipMalloc((void**)&s.d_rw, bytes)) != hipSuccess) {
-        s.h_rw.free();
-        s.d_rw = nullptr;
+}  // extern "C"
+
+// Buffers of the slot's per-packet scratch (Mapped or DeviceOnly), each allocated for max_pkts
+// elements with the context's first batch that needs it, in the order given.
+template <class Buf, class... More>
+static int slot_scratch(vpcsum_ctx* c, const char* entry, Buf& buf, More&... more) {
+    if (!buf.p) {
+        const hipError_t e = buf.alloc((size_t)c->max_pkts * sizeof(*buf.p));
+        if (e != hipSuccess) return fail("%s allocation: %s (%d)", entry, hipGetErrorString(e), (int)e);
     }
-    return e == hipSuccess ? 0 : hipfail(e, what);
+    if constexpr (sizeof...(More) > 0) return slot_scratch(c, entry, more...);
+    return 0;
+}
+
+// The staged transfers of a batch on its slot's stream.  Up: the n descriptors of h_desc, the
+// per-packet entries of h_rw (entry_bytes of them, 0: none) and the frames staged in h_arena.
+// Down: the out words, if wanted, and the status bytes into the pinned staging.
+static int stage_frames_up(Slot& s, uint64_t bytes) {
+    if (bytes) VPC_CHECK(hipMemcpyAsync(s.d_arena.p, s.h_arena.p, bytes, hipMemcpyHostToDevice, s.stream), "H2D frames");
+    return 0;
+}
+
+static int stage_up(Slot& s, uint32_t n, size_t entry_bytes, uint64_t frame_bytes) {
+    VPC_CHECK(hipMemcpyAsync(s.d_desc.p, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
+              "H2D descriptors");
+    if (entry_bytes) VPC_CHECK(hipMemcpyAsync(s.d_rw.p, s.h_rw.p, entry_bytes, hipMemcpyHostToDevice, s.stream), "H2D entries");
+    return stage_frames_up(s, frame_bytes);
+}
+
+static int stage_down(Slot& s, uint32_t n, bool out) {
+    if (out) VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
+    VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status.p, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
+    return 0;
+}
+
+// Where a batch's status bytes and out words will lie: the service's buffers or the slot's staging.
+static HandBack status_of(vpcsum_ctx* c, Slot& s, bool svc, uint8_t* h_status, uint32_t n) {
+    return {h_status, svc ? c->svc.h_status.p : s.h_status.p, n};
+}
+static HandBack out_of(vpcsum_ctx* c, Slot& s, bool svc, uint32_t* h_out, uint32_t n) {
+    return {h_out, svc ? c->svc.h_out.p : s.h_out.p, (size_t)n * 4};
 }
 
 // Zero-copy batches of up to kZeroCopyWaveTeams packets run one wave per packet (variant 12, 64
@@ -1174,84 +1168,95 @@ static int svc_post_frames(vpcsum_ctx* c, Slot& s, const Batch& b, uint64_t aren
     return svc_post(c, s, b, nullptr, arena_len, base, c->svc.h_desc.p, nullptr, 0, kSvcFrames | form, ticket);
 }
 
+// The shared start of the descriptor entries (submit, submit_pre, nat_submit), in two parts around
+// the checks an entry has of its own.  desc_args: the arguments every one of them refuses, under the
+// entry's name (`also`: the array it needs besides the descriptors; `nulls` names them all).
+static int desc_args(const vpcsum_ctx* c, const char* what, const char* nulls, const void* h_arena, const void* h_desc,
+                     const void* also, uint32_t n, const uint64_t* ticket) {
+    if (!c || !ticket) return fail("%s: NULL context or ticket", what);
+    if (n > c->max_pkts) return fail("%s: %u packets > capacity %u", what, n, c->max_pkts);
+    if (n && (!h_arena || !h_desc || !also)) return fail("%s: NULL %s", what, nulls);
+    return 0;
+}
+
+// desc_entry: the next slot, and where the batch's frames are.  body(s, b, sp, base) then runs the
+// batch under c->mu on c's device; b carries the ticket, n, mode and the caller's frames and
+// descriptors, sp is the span of the descriptors in the arena, and base the device address of
+// h_arena[0] when that span lies in a registered arena (zero-copy), else NULL (staged).
+template <class Body>
+static int desc_entry(vpcsum_ctx* c, uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc, uint32_t n,
+                      uint32_t mode, Body body) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    VPC_ON_DEVICE(c->device);
+    Batch b;
+    Slot* s = slot_acquire(c, &b.ticket);
+    if (!s) return -1;
+    b.n = n;
+    b.mode = mode;
+    b.user_arena = h_arena;
+    b.user_desc = h_desc;
+    const BatchSpan sp = batch_span(h_desc, n, arena_len);
+    uint8_t* dev_arena = sp.hi > sp.lo ? mapped_dev(c, h_arena + sp.lo, sp.hi - sp.lo) : nullptr;
+    return body(*s, b, sp, dev_arena ? dev_arena - sp.lo : nullptr);
+}
+
+extern "C" {
+
 int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc, uint32_t n,
                       uint32_t* h_out, uint8_t* h_status, uint32_t mode, uint64_t* ticket) {
     try {
-        if (!c || !ticket) return fail("vpcsum_ctx_submit: NULL context or ticket");
-        if (n > c->max_pkts) return fail("vpcsum_ctx_submit: %u packets > capacity %u", n, c->max_pkts);
-        if (n && (!h_arena || !h_desc)) return fail("vpcsum_ctx_submit: NULL arena or descriptors");
+        if (desc_args(c, "vpcsum_ctx_submit", "arena or descriptors", h_arena, h_desc, h_desc, n, ticket) != 0) return -1;
         if (mode & ~(VPCSUM_MODE_VERIFY | VPCSUM_MODE_WRITE)) return fail("vpcsum_ctx_submit: bad mode 0x%x", mode);
-        std::lock_guard<std::mutex> lk(c->mu);
-        VPC_ON_DEVICE(c->device);
-        Batch b;
-        Slot* slot = slot_acquire(c, &b.ticket);
-        if (!slot) return -1;
-        Slot& s = *slot;
-        b.n = n;
-        b.mode = mode;
-        b.user_arena = h_arena;
-        b.user_desc = h_desc;
-        b.user_out = h_out;
-        b.user_status = h_status;
-
-        const BatchSpan sp = batch_span(h_desc, n, arena_len);
-        const uint64_t lo = sp.lo, span = sp.hi - sp.lo;
-        uint8_t* dev_arena = span ? mapped_dev(c, h_arena + lo, span) : nullptr;
-        if (dev_arena) {
-            // Zero-copy: the frames live in a page-locked, mapped arena (an AF_XDP umem).  The
-            // kernel reads them over PCIe in place, takes the descriptors from and writes the
-            // results to pinned staging, and with MODE_WRITE stores the checksum fields straight
-            // into the frames -- no DMA copy in either direction.
-            uint8_t* base = dev_arena - lo;   // device address of h_arena[0]
-            if (c->svc.on && n <= kSvcBatchMax) {
-                if (svc_drain(c) != 0) return -1;
-                return svc_post(c, s, b, h_arena, arena_len, base, h_desc, nullptr, 0, 0, ticket);
-            }
-            memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-            // no out words asked for (an ingress verify: the status bytes are the result): none written
-            VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
-                                  (mode & VPCSUM_MODE_VERIFY) != 0, (mode & VPCSUM_MODE_WRITE) ? base : nullptr,
-                                  zero_copy_tune(n), s.stream),
-                      "checksum launch (zero-copy)");
-            b.zero_copy = true;
-        } else {
-            const bool gather = span > 2 * sp.used + (64u << 10);
-            uint64_t dev_len = span;
-            if (gather) {
-                // sparse batch in a large pageable arena: gather the touched 16-B blocks only
-                const int64_t staged = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena, c->max_arena);
-                if (staged < 0) return fail("vpcsum_ctx_submit: gathered batch exceeds capacity");
-                dev_len = (uint64_t)staged;
+        return desc_entry(c, h_arena, arena_len, h_desc, n, mode, [&](Slot& s, Batch& b, const BatchSpan& sp, uint8_t* base) {
+            const uint64_t lo = sp.lo, span = sp.hi - sp.lo;
+            const bool svc = base && c->svc.on && n <= kSvcBatchMax;
+            b.hand_back({status_of(c, s, svc, h_status, n), out_of(c, s, svc, h_out, n)});
+            if (base) {
+                // Zero-copy: the frames live in a page-locked, mapped arena (an AF_XDP umem).  The
+                // kernel reads them over PCIe in place, takes the descriptors from and writes the
+                // results to pinned staging, and with MODE_WRITE stores the checksum fields straight
+                // into the frames -- no DMA copy in either direction.
+                if (svc)
+                    return svc_drain(c) != 0 ? -1 : svc_post(c, s, b, h_arena, arena_len, base, h_desc, nullptr, 0, 0, ticket);
+                memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+                // no out words asked for (an ingress verify: the status bytes are the result): none written
+                VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
+                                      (mode & VPCSUM_MODE_VERIFY) != 0, (mode & VPCSUM_MODE_WRITE) ? base : nullptr,
+                                      zero_copy_tune(n), s.stream),
+                          "checksum launch (zero-copy)");
+                b.zero_copy = true;
             } else {
-                if (span > c->max_arena) return fail("vpcsum_ctx_submit: batch spans %llu bytes > capacity %llu",
-                                                     (unsigned long long)span, (unsigned long long)c->max_arena);
-                // descriptors rebased to the device copy of [lo, hi)
-                for (uint32_t i = 0; i < n; ++i) {
-                    s.h_desc.p[i] = h_desc[i];
-                    if (h_desc[i].l3_off >= lo) s.h_desc.p[i].l3_off = h_desc[i].l3_off - lo;
-                    else s.h_desc.p[i].l3_off = UINT64_MAX;   // out of span -> BAD in the kernel
+                const bool gather = span > 2 * sp.used + (64u << 10);
+                uint64_t dev_len = span;
+                if (gather) {
+                    // sparse batch in a large pageable arena: gather the touched 16-B blocks only
+                    const int64_t staged = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena.p, c->max_arena);
+                    if (staged < 0) return fail("vpcsum_ctx_submit: gathered batch exceeds capacity");
+                    dev_len = (uint64_t)staged;
+                } else {
+                    if (span > c->max_arena) return fail("vpcsum_ctx_submit: batch spans %llu bytes > capacity %llu",
+                                                         (unsigned long long)span, (unsigned long long)c->max_arena);
+                    // descriptors rebased to the device copy of [lo, hi)
+                    for (uint32_t i = 0; i < n; ++i) {
+                        s.h_desc.p[i] = h_desc[i];
+                        if (h_desc[i].l3_off >= lo) s.h_desc.p[i].l3_off = h_desc[i].l3_off - lo;
+                        else s.h_desc.p[i].l3_off = UINT64_MAX;   // out of span -> BAD in the kernel
+                    }
                 }
+                // through the pinned staging, always: the span lies in no arena this context registered
+                // (base is NULL), and the library never DMAs from memory it did not register (is_registered)
+                if (!gather && span) memcpy(s.h_arena.p, h_arena + lo, span);
+                if (stage_up(s, n, 0, dev_len) != 0) return -1;
+                // the out words travel when the caller asked for them or MODE_WRITE places them in the frames
+                const bool want_out = h_out || (mode & VPCSUM_MODE_WRITE);
+                VPC_CHECK(launch_csum(s.d_arena.p, dev_len, s.d_desc.p, n, want_out ? s.d_out.p : nullptr, s.d_status.p, nullptr,
+                                      (mode & VPCSUM_MODE_VERIFY) != 0, nullptr, CsumTune{}, s.stream),
+                          "checksum launch");
+                if (stage_down(s, n, want_out) != 0) return -1;
+                if (mode & VPCSUM_MODE_WRITE) b.scatter = Scatter::CsumFields;
             }
-            VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
-                      "H2D descriptors");
-            if (dev_len) {
-                const uint8_t* src = gather ? s.h_arena : h_arena + lo;
-                if (!gather && !is_registered(c, src, span)) {
-                    memcpy(s.h_arena, src, span);   // pageable -> pinned staging
-                    src = s.h_arena;
-                }
-                VPC_CHECK(hipMemcpyAsync(s.d_arena, src, dev_len, hipMemcpyHostToDevice, s.stream), "H2D arena");
-            }
-            // the out words travel when the caller asked for them or MODE_WRITE places them in the frames
-            const bool want_out = h_out || (mode & VPCSUM_MODE_WRITE);
-            VPC_CHECK(launch_csum(s.d_arena, dev_len, s.d_desc, n, want_out ? s.d_out : nullptr, s.d_status, nullptr,
-                                  (mode & VPCSUM_MODE_VERIFY) != 0, nullptr, CsumTune{}, s.stream),
-                      "checksum launch");
-            if (want_out)
-                VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
-            VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
-        }
-        return slot_commit(s, b, ticket);
+            return slot_commit(s, b, ticket);
+        });
     } VPC_CATCH("vpcsum_ctx_submit")
 }
 
@@ -1259,9 +1264,8 @@ int vpcsum_ctx_submit_pre(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
                           const void* h_pre, uint32_t pre_fmt, uint32_t n, uint32_t* h_out, uint8_t* h_status,
                           uint32_t mode, uint64_t* ticket) {
     try {
-        if (!c || !ticket) return fail("vpcsum_ctx_submit_pre: NULL context or ticket");
-        if (n > c->max_pkts) return fail("vpcsum_ctx_submit_pre: %u packets > capacity %u", n, c->max_pkts);
-        if (n && (!h_arena || !h_desc || !h_pre)) return fail("vpcsum_ctx_submit_pre: NULL arena, descriptors or pre-images");
+        if (desc_args(c, "vpcsum_ctx_submit_pre", "arena, descriptors or pre-images", h_arena, h_desc, h_pre, n, ticket) != 0)
+            return -1;
         if (pre_fmt > VPCSUM_PRE_FMT_PRE) return fail("vpcsum_ctx_submit_pre: bad pre_fmt %u", pre_fmt);
         if (mode & ~VPCSUM_MODE_WRITE) return fail("vpcsum_ctx_submit_pre: bad mode 0x%x (COMPUTE or WRITE)", mode);
         uint32_t npre = 0;
@@ -1270,79 +1274,63 @@ int vpcsum_ctx_submit_pre(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len,
         if (npre == 0) return vpcsum_ctx_submit(c, h_arena, arena_len, h_desc, n, h_out, h_status, mode, ticket);
         const size_t esz = pre_fmt == VPCSUM_PRE_FMT_PRE ? sizeof(vpcsum_pre_t) : sizeof(vpcsum_pre4_t);
         const bool full = npre < n;   // descriptors the checksum kernel sums in full
-        std::lock_guard<std::mutex> lk(c->mu);
-        VPC_ON_DEVICE(c->device);
-        Batch b;
-        Slot* slot = slot_acquire(c, &b.ticket);
-        if (!slot) return -1;
-        Slot& s = *slot;
-        b.n = n;
-        b.mode = mode;
-        b.user_arena = h_arena;
-        b.user_desc = h_desc;
-        b.user_out = h_out;
-        b.user_status = h_status;
-        const BatchSpan sp = batch_span(h_desc, n, arena_len);
-        uint8_t* dev_arena = sp.hi > sp.lo ? mapped_dev(c, h_arena + sp.lo, sp.hi - sp.lo) : nullptr;
-        uint8_t* base = dev_arena ? dev_arena - sp.lo : nullptr;   // device address of h_arena[0]
-        const uint32_t wr = mode & VPCSUM_MODE_WRITE;
-        // a small flush from the registered umem: the service grid, F_PRE frames and the others in
-        // one batch (kernels.hip svc_pre_packet)
-        if (dev_arena && c->svc.on && n <= kSvcBatchMax) {
-            if (svc_drain(c) != 0) return -1;
-            return svc_post(c, s, b, h_arena, arena_len, base, h_desc, h_pre, pre_fmt, 0, ticket);
-        }
-        if (slot_rw_alloc(c, s, "vpcsum_ctx_submit_pre allocation") != 0) return -1;
-        memcpy(s.h_rw.p, h_pre, (size_t)n * esz);
-        if (dev_arena) {
-            // registered arena (umem): in place; an F_PRE packet's header is all that crosses PCIe
-            memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-            if (full)
-                VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, s.h_out.dev, s.h_status.dev, nullptr, false,
-                                      wr ? base : nullptr, zero_copy_tune(n), s.stream),
-                          "checksum launch (zero-copy)");
-            VPC_CHECK(launch_pre(base, arena_len, s.h_desc.dev, s.h_rw.dev, n, s.h_out.dev, s.h_status.dev,
-                                 pre_build(wr, (int)pre_fmt), s.stream),
-                      "pre-image launch (zero-copy)");
-            b.zero_copy = true;
-        } else {
-            // staged: each packet's 16-B blocks gathered into the pinned staging -- of an F_PRE
-            // packet only its header (pre_staged_len; its descriptor's l3_len cut to that)
-            const int64_t pos = gather_blocks(
-                h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena, c->max_arena, [&](uint32_t i, const vpcsum_desc_t& d) {
-                    const uint8_t* e = (const uint8_t*)h_pre + (size_t)i * esz;
-                    bool cut;
-                    const uint32_t take = pre_staged_len(h_arena, d, e, pre_fmt, &cut);
-                    if (cut && (pre_entry_mask(e, pre_fmt) & VPCSUM_PRE_HSUM)) {
-                        // the kernel checks the record's segment length against the descriptor's,
-                        // which is cut here: check it against the real one on the host, and hand the
-                        // kernel the cut length (or, on a mismatch, a record it refuses)
-                        vpcsum_hsum_t hs;
-                        uint8_t* se = (uint8_t*)s.h_rw.p + (size_t)i * esz;
-                        memcpy(&hs, se, sizeof(hs));
-                        if (hs.l4_len == (uint32_t)d.l3_len - d.l4_off) hs.l4_len = (uint16_t)(take - d.l4_off);
-                        else hs.l2_len = 0;
-                        memcpy(se, &hs, sizeof(hs));
-                    }
-                    return take;
-                });
-            if (pos < 0) return fail("vpcsum_ctx_submit_pre: gathered batch exceeds capacity");
-            VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
-                      "H2D descriptors");
-            VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw.p, (size_t)n * esz, hipMemcpyHostToDevice, s.stream), "H2D pre-images");
-            if (pos) VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, pos, hipMemcpyHostToDevice, s.stream), "H2D frames");
-            if (full)
-                VPC_CHECK(launch_csum(s.d_arena, pos, s.d_desc, n, s.d_out, s.d_status, nullptr, false, nullptr,
-                                      CsumTune{}, s.stream),
-                          "checksum launch");
-            // the sums go back through out: slot_finish writes them into the caller's frames
-            VPC_CHECK(launch_pre(s.d_arena, pos, s.d_desc, s.d_rw, n, s.d_out, s.d_status, pre_build(0, (int)pre_fmt),
-                                 s.stream),
-                      "pre-image launch");
-            VPC_CHECK(hipMemcpyAsync(s.h_out.p, s.d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s.stream), "D2H out");
-            VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
-        }
-        return slot_commit(s, b, ticket);
+        return desc_entry(c, h_arena, arena_len, h_desc, n, mode, [&](Slot& s, Batch& b, const BatchSpan&, uint8_t* base) {
+            const uint32_t wr = mode & VPCSUM_MODE_WRITE;
+            const bool svc = base && c->svc.on && n <= kSvcBatchMax;
+            b.hand_back({status_of(c, s, svc, h_status, n), out_of(c, s, svc, h_out, n)});
+            // a small flush from the registered umem: the service grid, F_PRE frames and the others in
+            // one batch (kernels.hip svc_pre_packet)
+            if (svc)
+                return svc_drain(c) != 0 ? -1 : svc_post(c, s, b, h_arena, arena_len, base, h_desc, h_pre, pre_fmt, 0, ticket);
+            if (slot_scratch(c, "vpcsum_ctx_submit_pre", s.h_rw, s.d_rw) != 0) return -1;
+            memcpy(s.h_rw.p, h_pre, (size_t)n * esz);
+            if (base) {
+                // registered arena (umem): in place; an F_PRE packet's header is all that crosses PCIe
+                memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+                if (full)
+                    VPC_CHECK(launch_csum(base, arena_len, s.h_desc.dev, n, s.h_out.dev, s.h_status.dev, nullptr, false,
+                                          wr ? base : nullptr, zero_copy_tune(n), s.stream),
+                              "checksum launch (zero-copy)");
+                VPC_CHECK(launch_pre(base, arena_len, s.h_desc.dev, s.h_rw.dev, n, s.h_out.dev, s.h_status.dev,
+                                     pre_build(wr, (int)pre_fmt), s.stream),
+                          "pre-image launch (zero-copy)");
+                b.zero_copy = true;
+            } else {
+                // staged: each packet's 16-B blocks gathered into the pinned staging -- of an F_PRE
+                // packet only its header (pre_staged_len; its descriptor's l3_len cut to that)
+                const int64_t pos = gather_blocks(
+                    h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena.p, c->max_arena, [&](uint32_t i, const vpcsum_desc_t& d) {
+                        const uint8_t* e = (const uint8_t*)h_pre + (size_t)i * esz;
+                        bool cut;
+                        const uint32_t take = pre_staged_len(h_arena, d, e, pre_fmt, &cut);
+                        if (cut && (pre_entry_mask(e, pre_fmt) & VPCSUM_PRE_HSUM)) {
+                            // the kernel checks the record's segment length against the descriptor's,
+                            // which is cut here: check it against the real one on the host, and hand the
+                            // kernel the cut length (or, on a mismatch, a record it refuses)
+                            vpcsum_hsum_t hs;
+                            uint8_t* se = (uint8_t*)s.h_rw.p + (size_t)i * esz;
+                            memcpy(&hs, se, sizeof(hs));
+                            if (hs.l4_len == (uint32_t)d.l3_len - d.l4_off) hs.l4_len = (uint16_t)(take - d.l4_off);
+                            else hs.l2_len = 0;
+                            memcpy(se, &hs, sizeof(hs));
+                        }
+                        return take;
+                    });
+                if (pos < 0) return fail("vpcsum_ctx_submit_pre: gathered batch exceeds capacity");
+                if (stage_up(s, n, (size_t)n * esz, (uint64_t)pos) != 0) return -1;
+                if (full)
+                    VPC_CHECK(launch_csum(s.d_arena.p, pos, s.d_desc.p, n, s.d_out.p, s.d_status.p, nullptr, false, nullptr,
+                                          CsumTune{}, s.stream),
+                              "checksum launch");
+                // the sums go back through out: slot_finish writes them into the caller's frames
+                VPC_CHECK(launch_pre(s.d_arena.p, pos, s.d_desc.p, s.d_rw.p, n, s.d_out.p, s.d_status.p, pre_build(0, (int)pre_fmt),
+                                     s.stream),
+                          "pre-image launch");
+                if (stage_down(s, n, true) != 0) return -1;
+                if (wr) b.scatter = Scatter::CsumFields;
+            }
+            return slot_commit(s, b, ticket);
+        });
     } VPC_CATCH("vpcsum_ctx_submit_pre")
 }
 
@@ -1399,14 +1387,11 @@ static int ctx_verify_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t a
                              vpcsum_hsum_t* h_hsum, uint64_t* ticket, const char* what) {
     return frames_entry(c, what, "arena, frame table or status", h_arena, arena_len, h_frame_off, h_frame_len, h_status, n,
                         ticket, [&](Slot& s, Batch b, uint8_t* base, bool svc) {
-        if (h_hsum && n && !s.h_hs.p) {
-            const hipError_t e = s.h_hs.alloc((size_t)c->max_pkts * sizeof(vpcsum_hsum_t));
-            if (e != hipSuccess) return hipfail(e, what);
-        }
+        if (h_hsum && n && slot_scratch(c, what, s.h_hs) != 0) return -1;
         b.mode = VPCSUM_MODE_VERIFY;
-        b.user_out = h_out;
-        b.user_status = h_status;
-        b.user_hsum = n ? h_hsum : nullptr;
+        // the header sums: the service's aux buffer, or the slot's staging
+        b.hand_back({status_of(c, s, svc, h_status, n), out_of(c, s, svc, h_out, n),
+                     {h_hsum, svc ? (const void*)c->svc.h_pre.p : (const void*)s.h_hs.p, (size_t)n * sizeof(vpcsum_hsum_t)}});
         // a small received batch: the service grid parses and verifies each frame
         // (kernels.hip svc_frame_packet), the sums into its own buffer (copied out only with h_out),
         // the header sums into its aux buffer
@@ -1415,11 +1400,11 @@ static int ctx_verify_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t a
                                    h_hsum ? kSvcHsum : 0, ticket);
         if (n) {
             // parse the frames where they lie (zero-copy), then verify the descriptors it built
-            VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
+            VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc.p,
                                          nullptr, nullptr, s.stream, nullptr, h_hsum ? s.h_hs.dev : nullptr),
                       "parse launch");
             // h_out NULL: the status bytes alone (the out words are 4 of the 5 result bytes a packet writes)
-            VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
+            VPC_CHECK(launch_csum(base, arena_len, s.d_desc.p, n, h_out ? s.h_out.dev : nullptr, s.h_status.dev, nullptr,
                                   true, nullptr, zero_copy_tune(n), s.stream),
                       "verify launch");
         }
@@ -1453,8 +1438,7 @@ int vpcsum_ctx_egress_frames(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_l
         return frames_entry(c, "vpcsum_ctx_egress_frames", "arena, frame table or flags", h_arena, arena_len, h_frame_off,
                             h_frame_len, h_frame_flags, n, ticket, [&](Slot& s, Batch b, uint8_t* base, bool svc) {
             b.mode = VPCSUM_MODE_WRITE;
-            b.user_out = h_out;
-            b.user_status = h_status;
+            b.hand_back({status_of(c, s, svc, h_status, n), out_of(c, s, svc, h_out, n)});
             // a small flush: the service grid parses and sums each frame (kernels.hip svc_frame_packet)
             if (svc)
                 return svc_post_frames(c, s, b, arena_len, base, h_frame_off, h_frame_len, h_frame_flags, 0, 0, ticket);
@@ -1462,10 +1446,10 @@ int vpcsum_ctx_egress_frames(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_l
                 // the frames' own flags ride in the status staging: the parse reads them before the
                 // checksum kernel, later on the same stream, overwrites them with the statuses
                 memcpy(s.h_status.p, h_frame_flags, n);
-                VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, 0, s.d_desc, nullptr, nullptr,
+                VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, 0, s.d_desc.p, nullptr, nullptr,
                                              s.stream, s.h_status.dev),
                           "parse launch");
-                VPC_CHECK(launch_csum(base, arena_len, s.d_desc, n, s.h_out.dev, s.h_status.dev, nullptr, false,
+                VPC_CHECK(launch_csum(base, arena_len, s.d_desc.p, n, s.h_out.dev, s.h_status.dev, nullptr, false,
                                       base, zero_copy_tune(n), s.stream),
                           "checksum launch");
             }
@@ -1480,14 +1464,14 @@ int vpcsum_ctx_parse_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t ar
     try {
         return frames_entry(c, "vpcsum_ctx_parse_frames", "arena or frame table", h_arena, arena_len, h_frame_off,
                             h_frame_len, h_arena, n, ticket, [&](Slot& s, Batch b, uint8_t* base, bool svc) {
-            if (!s.h_tu.p) {
-                const hipError_t e = s.h_tu.alloc((size_t)c->max_pkts * sizeof(vpcsum_tuple_t));
-                if (e != hipSuccess) return hipfail(e, "vpcsum_ctx_parse_frames allocation");
-            }
-            b.kind = BatchKind::Parse;
-            b.user_status = h_status;
-            b.user_desc_out = h_desc;
-            b.user_tuples = h_tuples;
+            if (slot_scratch(c, "vpcsum_ctx_parse_frames", s.h_tu) != 0) return -1;
+            // descriptors and tuples: the pinned staging, or the service's aux buffer (the tuples
+            // behind room for kSvcBatchMax descriptors)
+            const uint8_t* aux = c->svc.h_pre.p;
+            b.hand_back({status_of(c, s, svc, h_status, n),
+                         {h_desc, svc ? (const void*)aux : (const void*)s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t)},
+                         {h_tuples, svc ? (const void*)(aux + (size_t)kSvcBatchMax * sizeof(vpcsum_desc_t)) : (const void*)s.h_tu.p,
+                          (size_t)n * sizeof(vpcsum_tuple_t)}});
             // a small received batch: the service grid parses each frame (kernels.hip svc_frame_packet)
             if (svc)
                 return svc_post_frames(c, s, b, arena_len, base, h_frame_off, h_frame_len, nullptr, VPCSUM_F_IP | VPCSUM_F_L4,
@@ -1506,53 +1490,39 @@ int vpcsum_ctx_parse_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t ar
 int vpcsum_ctx_nat_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc,
                           const vpcsum_nat_t* h_rw, uint32_t n, uint8_t* h_status, uint32_t nat_mode, uint64_t* ticket) {
     try {
-        if (!c || !ticket) return fail("vpcsum_ctx_nat_submit: NULL context or ticket");
-        if (n > c->max_pkts) return fail("vpcsum_ctx_nat_submit: %u packets > capacity %u", n, c->max_pkts);
-        if (n && (!h_arena || !h_desc || !h_rw)) return fail("vpcsum_ctx_nat_submit: NULL arena, descriptors or rewrites");
+        if (desc_args(c, "vpcsum_ctx_nat_submit", "arena, descriptors or rewrites", h_arena, h_desc, h_rw, n, ticket) != 0)
+            return -1;
         if (nat_mode & ~kNatCtxModeAccept)
             return fail("vpcsum_ctx_nat_submit: bad nat_mode 0x%x", nat_mode);
         // without the status bytes the caller would never see S_MSS_ABSENT, its part of the clamp
         if ((nat_mode & VPCSUM_NAT_TCP_REWRITES) && !h_status)
             return fail("vpcsum_ctx_nat_submit: VPCSUM_NAT_TCP_REWRITES needs a status buffer");
-        std::lock_guard<std::mutex> lk(c->mu);
-        VPC_ON_DEVICE(c->device);
-        Batch b;
-        Slot* slot = slot_acquire(c, &b.ticket);
-        if (!slot) return -1;
-        Slot& s = *slot;
-        b.kind = BatchKind::Nat;
-        b.n = n;
-        b.mode = nat_mode;
-        b.user_arena = h_arena;
-        b.user_desc = h_desc;
-        b.user_status = h_status;
-        if (slot_rw_alloc(c, s, "vpcsum_ctx_nat_submit") != 0) return -1;
-        const BatchSpan sp = batch_span(h_desc, n, arena_len);
-        uint8_t* dev_arena = sp.hi > sp.lo ? mapped_dev(c, h_arena + sp.lo, sp.hi - sp.lo) : nullptr;
-        memcpy(s.h_rw.p, h_rw, (size_t)n * sizeof(vpcsum_nat_t));
-        if (dev_arena) {
-            // the frames live in a registered (page-locked, mapped) arena: rewritten where they lie
-            memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-            if (n && nat_run(dev_arena - sp.lo, arena_len, s.h_desc.dev, s.h_rw.dev, 1, n, s.h_status.dev, nat_mode, s.stream) != 0)
-                return -1;
-            b.zero_copy = true;
-        } else {
-            // staged: each packet's 16-B blocks gathered into the pinned staging, rewritten on the
-            // device, and the whole gathered batch copied back (the headers return at wait)
-            const int64_t pos = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena, c->max_arena);
-            if (pos < 0) return fail("vpcsum_ctx_nat_submit: batch exceeds the staging capacity");
-            if (n) {
-                VPC_CHECK(hipMemcpyAsync(s.d_desc, s.h_desc.p, (size_t)n * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice, s.stream),
-                          "H2D descriptors");
-                VPC_CHECK(hipMemcpyAsync(s.d_rw, s.h_rw.p, (size_t)n * sizeof(vpcsum_nat_t), hipMemcpyHostToDevice, s.stream),
-                          "H2D rewrites");
-                if (pos) VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, pos, hipMemcpyHostToDevice, s.stream), "H2D frames");
-                if (nat_run(s.d_arena, pos, s.d_desc, s.d_rw, 1, n, s.d_status, nat_mode, s.stream) != 0) return -1;
-                if (pos) VPC_CHECK(hipMemcpyAsync(s.h_arena, s.d_arena, pos, hipMemcpyDeviceToHost, s.stream), "D2H frames");
-                VPC_CHECK(hipMemcpyAsync(s.h_status.p, s.d_status, n, hipMemcpyDeviceToHost, s.stream), "D2H status");
+        return desc_entry(c, h_arena, arena_len, h_desc, n, nat_mode, [&](Slot& s, Batch& b, const BatchSpan&, uint8_t* base) {
+            b.hand_back({status_of(c, s, false, h_status, n)});
+            if (slot_scratch(c, "vpcsum_ctx_nat_submit", s.h_rw, s.d_rw) != 0) return -1;
+            memcpy(s.h_rw.p, h_rw, (size_t)n * sizeof(vpcsum_nat_t));
+            if (base) {
+                // the frames live in a registered (page-locked, mapped) arena: rewritten where they lie
+                memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+                if (n && nat_run(base, arena_len, s.h_desc.dev, s.h_rw.dev, 1, n, s.h_status.dev, nat_mode, s.stream) != 0)
+                    return -1;
+                b.zero_copy = true;
+            } else {
+                // staged: each packet's 16-B blocks gathered into the pinned staging, rewritten on the
+                // device, and the whole gathered batch copied back (the headers return at wait: L3 header
+                // through the L4 checksum field, the TCP header too under VPCSUM_NAT_TCP_REWRITES)
+                const int64_t pos = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena.p, c->max_arena);
+                if (pos < 0) return fail("vpcsum_ctx_nat_submit: batch exceeds the staging capacity");
+                if (n) {
+                    if (stage_up(s, n, (size_t)n * sizeof(vpcsum_nat_t), (uint64_t)pos) != 0) return -1;
+                    if (nat_run(s.d_arena.p, pos, s.d_desc.p, s.d_rw.p, 1, n, s.d_status.p, nat_mode, s.stream) != 0) return -1;
+                    if (pos) VPC_CHECK(hipMemcpyAsync(s.h_arena.p, s.d_arena.p, pos, hipMemcpyDeviceToHost, s.stream), "D2H frames");
+                    if (stage_down(s, n, false) != 0) return -1;
+                }
+                b.scatter = Scatter::NatHeaders;
             }
-        }
-        return slot_commit(s, b, ticket);
+            return slot_commit(s, b, ticket);
+        });
     } VPC_CATCH("vpcsum_ctx_nat_submit")
 }
 
@@ -1601,15 +1571,30 @@ static void sort_unique(std::vector<uint32_t>& v) {
     v.erase(std::unique(v.begin(), v.end()), v.end());
 }
 
-// The lookup of a batch on the table's device; caller holds f->mu (max_probe and the launch are one
-// step against a concurrent update).
-// d_fp != NULL: the lookup that also writes the flows' Fastpath records.
-static int flow_lookup_locked(vpcsum_flowtab* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
-                              uint8_t* d_verdict, vpcsum_fastpath_t* d_fp, hipStream_t s) {
+// The lookup of a batch under f->mu (max_probe and the launch are one step against a concurrent
+// update); the caller is on the table's device.  d_fp != NULL: the lookup that also writes the
+// flows' Fastpath records.
+static int flow_lookup(vpcsum_flowtab* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw, uint8_t* d_verdict,
+                       vpcsum_fastpath_t* d_fp, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(f->mu);
     VPC_CHECK(launch_flow_lookup(f->d_slots, f->t->mask(), f->t->max_probe(), f->d_touched, d_tuples, n, d_rw, d_verdict,
                                  d_fp, s),
               "flow lookup launch");
     return 0;
+}
+
+// vpcsum_flow_lookup_async (fp false, d_fp NULL) / vpcsum_flow_lookup_fp_async
+static int flow_lookup_async(const char* what, bool fp, vpcsum_flowtab* f, const vpcsum_tuple_t* d_tuples, uint32_t n,
+                             vpcsum_nat_t* d_rw, uint8_t* d_verdict, vpcsum_fastpath_t* d_fp, void* stream) {
+    if (!f) return fail("%s: NULL table", what);
+    if (n == 0) return 0;
+    if (!d_tuples || !d_rw || !d_verdict || (fp && !d_fp))
+        return fail("%s: NULL tuples, entries%s", what, fp ? ", verdicts or Fastpath records" : " or verdicts");
+    if (((uintptr_t)d_tuples | (uintptr_t)d_rw | (uintptr_t)d_fp) & 3)
+        return fail("%s: tuples / entries%s not 4-byte aligned", what, fp ? " / Fastpath records" : "");
+    if (n > (1u << 28)) return fail("%s: %u packets > 2^28", what, n);
+    VPC_ON_DEVICE(f->device);
+    return flow_lookup(f, d_tuples, n, d_rw, d_verdict, d_fp, (hipStream_t)stream);
 }
 
 // The mirror's changed slots to the device on stream s, and the wait for them (so that the mirror is
@@ -1726,14 +1711,7 @@ int vpcsum_flow_hash(const vpcsum_tuple_t* key, uint64_t* out) {
 int vpcsum_flow_lookup_async(vpcsum_flowtab_t* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
                              uint8_t* d_verdict, void* stream) {
     try {
-        if (!f) return fail("vpcsum_flow_lookup_async: NULL table");
-        if (n == 0) return 0;
-        if (!d_tuples || !d_rw || !d_verdict) return fail("vpcsum_flow_lookup_async: NULL tuples, entries or verdicts");
-        if (((uintptr_t)d_tuples | (uintptr_t)d_rw) & 3) return fail("vpcsum_flow_lookup_async: tuples / entries not 4-byte aligned");
-        if (n > (1u << 28)) return fail("vpcsum_flow_lookup_async: %u packets > 2^28", n);
-        std::lock_guard<std::mutex> lk(f->mu);
-        VPC_ON_DEVICE(f->device);
-        return flow_lookup_locked(f, d_tuples, n, d_rw, d_verdict, nullptr, (hipStream_t)stream);
+        return flow_lookup_async("vpcsum_flow_lookup_async", false, f, d_tuples, n, d_rw, d_verdict, nullptr, stream);
     } VPC_CATCH("vpcsum_flow_lookup_async")
 }
 
@@ -1759,16 +1737,7 @@ int vpcsum_flowtab_set_fastpath(vpcsum_flowtab_t* f, const vpcsum_tuple_t* h_key
 int vpcsum_flow_lookup_fp_async(vpcsum_flowtab_t* f, const vpcsum_tuple_t* d_tuples, uint32_t n, vpcsum_nat_t* d_rw,
                                 uint8_t* d_verdict, vpcsum_fastpath_t* d_fp, void* stream) {
     try {
-        if (!f) return fail("vpcsum_flow_lookup_fp_async: NULL table");
-        if (n == 0) return 0;
-        if (!d_tuples || !d_rw || !d_verdict || !d_fp)
-            return fail("vpcsum_flow_lookup_fp_async: NULL tuples, entries, verdicts or Fastpath records");
-        if (((uintptr_t)d_tuples | (uintptr_t)d_rw | (uintptr_t)d_fp) & 3)
-            return fail("vpcsum_flow_lookup_fp_async: tuples / entries / Fastpath records not 4-byte aligned");
-        if (n > (1u << 28)) return fail("vpcsum_flow_lookup_fp_async: %u packets > 2^28", n);
-        std::lock_guard<std::mutex> lk(f->mu);
-        VPC_ON_DEVICE(f->device);
-        return flow_lookup_locked(f, d_tuples, n, d_rw, d_verdict, d_fp, (hipStream_t)stream);
+        return flow_lookup_async("vpcsum_flow_lookup_fp_async", true, f, d_tuples, n, d_rw, d_verdict, d_fp, stream);
     } VPC_CATCH("vpcsum_flow_lookup_fp_async")
 }
 
@@ -1847,35 +1816,25 @@ static int ctx_nat_flow_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uint8_t* h_
     // the service grid has no lookup: the batch is launched whatever its size (may_svc false)
     return frames_entry(c, what, "arena, frame table or status", h_arena, arena_len, h_frame_off, h_frame_len, h_status, n,
                         ticket, [&](Slot& s, Batch b, uint8_t* base, bool) {
-        b.kind = BatchKind::Nat;   // zero-copy: the frames are rewritten where they lie
-        b.mode = nat_mode;
-        b.user_status = h_status;
-        b.user_verdict = h_verdict;
-        b.user_port = forward && n ? h_port : nullptr;
+        b.mode = nat_mode;   // zero-copy: the frames are rewritten where they lie
         if (n) {
-            // per-packet scratch of the chain, sized from max_pkts with the context's first such
-            // batch: tuples and entries on the device, verdicts in pinned memory
-            if (slot_rw_alloc(c, s, what) != 0) return -1;
-            if (!s.d_tu) VPC_CHECK(hipMalloc((void**)&s.d_tu, (size_t)c->max_pkts * sizeof(vpcsum_tuple_t)), what);
-            if (!s.h_verdict.p) VPC_CHECK(s.h_verdict.alloc(c->max_pkts), what);
-            // a forwarding batch: Fastpath records on the device, ports in pinned memory
-            if (forward && !s.d_fp) VPC_CHECK(hipMalloc((void**)&s.d_fp, (size_t)c->max_pkts * sizeof(vpcsum_fastpath_t)), what);
-            if (forward && !s.h_port.p) VPC_CHECK(s.h_port.alloc((size_t)c->max_pkts * 4), what);
+            // per-packet scratch of the chain: entries and tuples on the device, verdicts in pinned
+            // memory; a forwarding batch: Fastpath records on the device, ports in pinned memory
+            if (slot_scratch(c, what, s.h_rw, s.d_rw, s.d_tu, s.h_verdict) != 0) return -1;
+            if (forward && slot_scratch(c, what, s.d_fp, s.h_port) != 0) return -1;
+            b.hand_back({status_of(c, s, false, h_status, n), {h_verdict, s.h_verdict.p, n},
+                         {forward ? h_port : nullptr, s.h_port.p, (size_t)n * 4}});
             // parse -> tuples -> lookup -> entries -> rewrite (-> L2 write), one stream; the parse's
             // status bytes are not needed: a refused frame's descriptor is all zeros, which the
             // rewrite refuses (S_BAD_DESC, nothing written)
-            VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc,
-                                         nullptr, s.d_tu, s.stream),
+            VPC_CHECK(launch_parse_ether(base, arena_len, s.h_foff.dev, s.h_flen.dev, n, VPCSUM_F_IP | VPCSUM_F_L4, s.d_desc.p,
+                                         nullptr, s.d_tu.p, s.stream),
                       "parse launch");
-            {
-                std::lock_guard<std::mutex> lf(f->mu);
-                if (flow_lookup_locked(f, s.d_tu, n, s.d_rw, s.h_verdict.dev, forward ? s.d_fp : nullptr, s.stream) != 0)
-                    return -1;
-            }
-            if (nat_run(base, arena_len, s.d_desc, s.d_rw, 1, n, s.h_status.dev, nat_mode, s.stream) != 0) return -1;
+            if (flow_lookup(f, s.d_tu.p, n, s.d_rw.p, s.h_verdict.dev, forward ? s.d_fp.p : nullptr, s.stream) != 0) return -1;
+            if (nat_run(base, arena_len, s.d_desc.p, s.d_rw.p, 1, n, s.h_status.dev, nat_mode, s.stream) != 0) return -1;
             // the rewrite's status says which HIT frames are complete: those get their flow's addresses
             if (forward)
-                VPC_CHECK(launch_l2_forward(base, arena_len, s.h_foff.dev, s.h_flen.dev, s.h_verdict.dev, s.h_status.dev, s.d_fp,
+                VPC_CHECK(launch_l2_forward(base, arena_len, s.h_foff.dev, s.h_flen.dev, s.h_verdict.dev, s.h_status.dev, s.d_fp.p,
                                             n, s.h_port.dev, s.stream),
                           "L2 forward launch");
         }
@@ -1922,49 +1881,29 @@ int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_le
         // the source: read in place when registered, else the span of the payloads that lie inside it
         const uint8_t* src_dev = n && src_len ? mapped_dev(c, h_src, src_len) : nullptr;
         const bool staged = n && src_len && !src_dev;
-        uint64_t lo = UINT64_MAX, hi = 0;
-        if (staged) {
-            for (uint32_t i = 0; i < n; ++i) {
-                const vpcsum_tcpseg_t& r = h_seg[i];
-                if (!r.data_len || r.data_off > src_len || r.data_len > src_len - r.data_off) continue;
-                lo = std::min(lo, r.data_off);
-                hi = std::max(hi, r.data_off + r.data_len);
-            }
-            if (hi > lo && hi - lo > c->max_arena)
-                return fail("%s: the payloads span %llu bytes > capacity %llu", what, (unsigned long long)(hi - lo),
-                            (unsigned long long)c->max_arena);
-        }
-        const uint64_t span = hi > lo ? hi - lo : 0;
+        TcpPayloadSpan sp = {0, 0};
+        if (staged && !tcp_build_payload_span(h_seg, n, src_len, c->max_arena, &sp))
+            return fail("%s: the payloads span %llu bytes > capacity %llu", what, (unsigned long long)sp.len,
+                        (unsigned long long)c->max_arena);
         Batch b;
         Slot* slot = slot_acquire(c, &b.ticket);
         if (!slot) return -1;
         Slot& s = *slot;
         b.n = n;
         b.zero_copy = true;   // the frames are written in place through the destination's mapping
-        b.user_out = h_out;
-        b.user_status = h_status;
-        b.user_flen = n ? h_frame_len : nullptr;
         if (n) {
-            // records, templates and frame lengths: pinned, sized from max_pkts with the context's first build
-            if (!s.h_tseg.p) VPC_CHECK(s.h_tseg.alloc((size_t)c->max_pkts * sizeof(vpcsum_tcpseg_t)), what);
-            if (!s.h_thdr.p) VPC_CHECK(s.h_thdr.alloc((size_t)c->max_pkts * sizeof(vpcsum_tcphdr_t)), what);
-            if (!s.h_tlen.p) VPC_CHECK(s.h_tlen.alloc((size_t)c->max_pkts * 4), what);
+            // records, templates and frame lengths: pinned
+            if (slot_scratch(c, what, s.h_tseg, s.h_thdr, s.h_tlen) != 0) return -1;
+            b.hand_back({status_of(c, s, false, h_status, n), {h_frame_len, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
             memcpy(s.h_tseg.p, h_seg, (size_t)n * sizeof(vpcsum_tcpseg_t));
             if (n_hdr) memcpy(s.h_thdr.p, h_hdr, (size_t)n_hdr * sizeof(vpcsum_tcphdr_t));
             if (staged) {
-                // the library's copy of the records names the staged span; a payload outside the
-                // source stays outside (refused by the kernel), an empty one reads nothing
-                for (uint32_t i = 0; i < n; ++i) {
-                    vpcsum_tcpseg_t& r = s.h_tseg.p[i];
-                    if (r.data_off > src_len || r.data_len > src_len - r.data_off) r.data_off = UINT64_MAX;
-                    else r.data_off = r.data_len ? r.data_off - lo : 0;
-                }
-                if (span) {
-                    memcpy(s.h_arena, h_src + lo, span);   // pageable -> pinned staging
-                    VPC_CHECK(hipMemcpyAsync(s.d_arena, s.h_arena, span, hipMemcpyHostToDevice, s.stream), "H2D payloads");
-                }
+                // the library's copy of the records names the staged span
+                tcp_build_rebase_payloads(s.h_tseg.p, n, src_len, sp.lo);
+                if (sp.len) memcpy(s.h_arena.p, h_src + sp.lo, sp.len);   // pageable -> pinned staging
+                if (stage_frames_up(s, sp.len) != 0) return -1;
             }
-            VPC_CHECK(launch_tcp_build(base, dst_len, staged ? s.d_arena : src_dev, staged ? span : src_len, s.h_thdr.dev, n_hdr,
+            VPC_CHECK(launch_tcp_build(base, dst_len, staged ? s.d_arena.p : src_dev, staged ? sp.len : src_len, s.h_thdr.dev, n_hdr,
                                        s.h_tseg.dev, n, s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
                       "TCP build launch");
         }
@@ -2027,16 +1966,16 @@ int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint
             Slot& s = c->slots[k & 1];
             // descriptors of this chunk address the device slot as frame (i - i0) * stride: the
             // caller's descriptors are relative to frame i0 once i0 * stride is subtracted
-            VPC_CHECK_DRAIN(hipMemcpyAsync(s.d_desc, h_desc + i0, (size_t)m * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice,
+            VPC_CHECK_DRAIN(hipMemcpyAsync(s.d_desc.p, h_desc + i0, (size_t)m * sizeof(vpcsum_desc_t), hipMemcpyHostToDevice,
                                      s.stream),
                       "pipeline H2D desc");
-            VPC_CHECK_DRAIN(hipMemcpy2DAsync(s.d_arena, stride, h_arena + (uint64_t)i0 * stride, stride, copy_bytes, m,
+            VPC_CHECK_DRAIN(hipMemcpy2DAsync(s.d_arena.p, stride, h_arena + (uint64_t)i0 * stride, stride, copy_bytes, m,
                                        hipMemcpyHostToDevice, s.stream),
                       "pipeline H2D frames");
-            VPC_CHECK_DRAIN(launch_csum(s.d_arena - (uint64_t)i0 * stride, (uint64_t)(i0 + m) * stride, s.d_desc, m, s.d_out,
+            VPC_CHECK_DRAIN(launch_csum(s.d_arena.p - (uint64_t)i0 * stride, (uint64_t)(i0 + m) * stride, s.d_desc.p, m, s.d_out.p,
                                   nullptr, nullptr, (mode & VPCSUM_MODE_VERIFY) != 0, w, CsumTune{}, s.stream),
                       "pipeline launch");
-            VPC_CHECK_DRAIN(hipMemcpyAsync(h_out + i0, s.d_out, (size_t)m * 4, hipMemcpyDeviceToHost, s.stream), "pipeline D2H");
+            VPC_CHECK_DRAIN(hipMemcpyAsync(h_out + i0, s.d_out.p, (size_t)m * 4, hipMemcpyDeviceToHost, s.stream), "pipeline D2H");
         }
     #undef VPC_CHECK_DRAIN
         hipError_t es = hipSuccess;   // both streams are joined, the first error is reported

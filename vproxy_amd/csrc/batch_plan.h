@@ -88,6 +88,37 @@ inline uint32_t nat_tcp_header_end(const vpcsum_desc_t& d) {
     return nat_header_end(d);
 }
 
+// The header return of a finished staged NAT batch: what the rewrite can have changed of packet i
+// (nat_header_end; `tcp`, under VPCSUM_NAT_TCP_REWRITES: nat_tcp_header_end) goes from the staging at
+// stage_desc[i] (gather_blocks' descriptor) into the caller's frame at desc[i]; not if refused (S_BAD_DESC).
+inline void return_nat_headers(uint8_t* arena, const vpcsum_desc_t* desc, const uint8_t* stage, const vpcsum_desc_t* stage_desc,
+                               const uint8_t* status, uint32_t n, bool tcp) {
+    for (uint32_t i = 0; i < n; ++i) {
+        if (status[i] & VPCSUM_S_BAD_DESC) continue;
+        const vpcsum_desc_t& d = desc[i];
+        memcpy(arena + d.l3_off, stage + stage_desc[i].l3_off, tcp ? nat_tcp_header_end(d) : nat_header_end(d));
+    }
+}
+
+// The placement of a finished staged MODE_WRITE batch: out[i] -- the IP sum in the low half, the L4
+// sum in the high half -- into the checksum fields of the caller's frames (big endian, as
+// ByteArray.int16).  A packet the kernel refused (S_BAD_DESC) is untouched.
+inline void place_checksums(uint8_t* arena, const vpcsum_desc_t* desc, const uint32_t* out, const uint8_t* status, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const vpcsum_desc_t& d = desc[i];
+        if (status[i] & VPCSUM_S_BAD_DESC) continue;
+        uint8_t* l3 = arena + d.l3_off;
+        const uint32_t w = out[i];
+        if (d.flags & VPCSUM_F_IP) { l3[10] = (uint8_t)(w >> 8); l3[11] = (uint8_t)w; }
+        if (d.flags & (VPCSUM_F_L4 | VPCSUM_F_L4P)) {
+            const int fld = l4_field_host(d.l4_proto);
+            if (fld < 0) continue;   // no L4 sum: the kernel refused the descriptor (BAD above)
+            l3[d.l4_off + fld] = (uint8_t)(w >> 24);
+            l3[d.l4_off + fld + 1] = (uint8_t)(w >> 16);
+        }
+    }
+}
+
 // The mask byte of a pre-image entry (vpcsum_pre_t / vpcsum_pre4_t).
 inline uint8_t pre_entry_mask(const void* entry, uint32_t pre_fmt) {
     return ((const uint8_t*)entry)[pre_fmt == VPCSUM_PRE_FMT_PRE ? offsetof(vpcsum_pre_t, mask) : offsetof(vpcsum_pre4_t, mask)];

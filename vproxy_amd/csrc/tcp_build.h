@@ -164,4 +164,34 @@ inline uint32_t tcp_build_header_bytes(const TcpBuildWords& w, const uint32_t (&
 }
 #endif
 
+// Host: the payloads of a batch whose source is staged (vpcsum_ctx_build_tcp_frames, a pageable
+// source).  The span [lo, lo + len) covers every non-empty payload that lies inside the source, by
+// tcp_build_fits' source rule (nothing wraps: data_off and src_len - data_off are compared, never
+// data_off + data_len with an unchecked data_off); len 0: there is none.  False: the span is longer
+// than `capacity`, the staging's room.
+struct TcpPayloadSpan { uint64_t lo, len; };
+inline bool tcp_build_payload_span(const vpcsum_tcpseg_t* seg, uint32_t n, uint64_t src_len, uint64_t capacity,
+                                   TcpPayloadSpan* sp) {
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const vpcsum_tcpseg_t& r = seg[i];
+        if (!r.data_len || r.data_off > src_len || r.data_len > src_len - r.data_off) continue;
+        if (r.data_off < lo) lo = r.data_off;
+        if (r.data_off + r.data_len > hi) hi = r.data_off + r.data_len;
+    }
+    *sp = hi > lo ? TcpPayloadSpan{lo, hi - lo} : TcpPayloadSpan{0, 0};
+    return sp->len <= capacity;
+}
+
+// The records of such a batch, in the library's copy, name the staged span instead of the source: a
+// payload outside the source stays outside (UINT64_MAX: refused by the kernel), an empty one reads
+// nothing (0), every other one is rebased to lo.
+inline void tcp_build_rebase_payloads(vpcsum_tcpseg_t* seg, uint32_t n, uint64_t src_len, uint64_t lo) {
+    for (uint32_t i = 0; i < n; ++i) {
+        vpcsum_tcpseg_t& r = seg[i];
+        if (r.data_off > src_len || r.data_len > src_len - r.data_off) r.data_off = UINT64_MAX;
+        else r.data_off = r.data_len ? r.data_off - lo : 0;
+    }
+}
+
 }  // namespace vpcsum
