@@ -48,8 +48,9 @@ extern "C" {
  * Additive since (the version stays 4): VPCSUM_NAT_TCP entries under the nat_mode bit
  * VPCSUM_NAT_TCP_REWRITES; a library from before answers that bit with "bad nat_mode", which is
  * how a caller probes for it; the flow table and its Fastpath; the TCP segment build
- * (vpcsum_tcp_build_async, vpcsum_ctx_build_tcp_frames, VPCsum.buildTcpFrames): new symbols, which a
- * caller probes for by looking them up. */
+ * (vpcsum_tcp_build_async, vpcsum_ctx_build_tcp_frames, VPCsum.buildTcpFrames) and the TCP receive
+ * (vpcsum_tcp_recv_async, vpcsum_tcp_digest_async, vpcsum_ctx_recv_tcp_frames, VPCsum.recvTcpFrames):
+ * new symbols, which a caller probes for by looking them up. */
 #define VPCSUM_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -492,6 +493,65 @@ int vpcsum_tcp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_sr
                            const vpcsum_tcphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* d_seg, uint32_t n,
                            uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream);
 
+/* TCP receive (additive, the ABI version stays 4): the build's mirror.  What the userspace TCP stack
+ * does on the host for every data segment it receives -- TcpStack.handleTcpEstablished ->
+ * receivingQueue.store(new Segment(seq, tcpPkt.getData())), TcpStack.java:302-306; ReceivingQueue.store
+ * trims what was already received and copies the rest out of the RX chunk, TcpEntry.java:390-426 --
+ * fused into the ingress verify: the segment is read once, its TCP sum recomputed and compared with
+ * the stored field, and the payload bytes past `skip` stored into the connection's receive buffer
+ * from the registers that summed them.  This call REPLACES vpcsum_compute_async / VPCSUM_MODE_VERIFY
+ * for the frames it is given; it does not come on top of it.
+ *
+ * THE BYTES ARE STORED WHATEVER THE VERDICT: the sum is only known once the last byte has passed.
+ * The caller advances expectingSeq only on VPCSUM_S_L4_OK; what it did not accept is overwritten by
+ * the next batch. */
+#define VPCSUM_TCPRX_STORE 0x01u
+typedef struct vpcsum_tcprx {   /* one per descriptor; 16 bytes, 8-byte aligned */
+    uint64_t dst_off;  /* where payload byte `skip` goes in the receive arena, any alignment */
+    uint32_t dst_cap;  /* room at dst_off; a segment that needs more is refused */
+    uint16_t skip;     /* leading payload bytes already received: store()'s incr = expectingSeq - seq */
+    uint8_t  ops;      /* VPCSUM_TCPRX_STORE, or 0: verify only (pure ACKs, segments store() would drop) */
+    uint8_t  rsv;      /* must be 0 */
+} vpcsum_tcprx_t;
+
+typedef struct vpcsum_tcpinfo { /* 16 bytes: what TcpStack reads of a segment before it decides */
+    uint32_t seq, ack;          /* host order */
+    uint16_t window, data_len;  /* host order; data_len = l3_len - l4_off - hlen */
+    uint8_t  hlen;              /* data offset * 4 (20..60); 0: no record, the rest 0 */
+    uint8_t  flags;             /* uint16 at 12 & 0x3f, as vpcsum_tuple_t.tcp_flags */
+    uint8_t  rsv[2];
+} vpcsum_tcpinfo_t;
+
+/* Descriptor i (as vpcsum_parse_ether_async writes them) pairs with record i.  With hlen the TCP data
+ * offset * 4 and data_len = l3_len - l4_off - hlen, a record that is not refused gets
+ *   d_status[i], d_out[i] (each may be NULL): exactly what vpcsum_compute_async writes for the
+ *     descriptor with VPCSUM_MODE_VERIFY -- S_DONE; S_L4_OK iff the stored TCP field equals the
+ *     recomputed sum (exact: a stored 0xffff against a recomputed 0x0000 is not OK); S_IP_OK iff the
+ *     descriptor has F_IP and the IPv4 header sum matches; d_out the recomputed sums;
+ *   with VPCSUM_TCPRX_STORE: segment bytes [hlen + skip, l3_len - l4_off) at d_dst + dst_off and
+ *     d_stored[i] (required) = data_len - skip; without it d_stored[i] = 0 and d_dst is not written.
+ * L2 padding after l3_len is neither read nor summed.  No byte outside [dst_off, dst_off + stored) is
+ * written.  A record is refused -- d_stored[i] 0, d_out[i] 0, S_BAD_DESC, not one byte written to
+ * d_dst, nothing of the arena read but the TCP header's first 16 bytes, and those only when the
+ * descriptor's bounds allow -- when l4_proto != 6; l3_ver is not 4 / 6; the descriptor lacks F_L4 or
+ * carries F_L4P, F_RAW or F_PRE; F_IP on IPv6; l4_off > l3_len, or an l4_off vpcsum_compute_async
+ * refuses (IPv4: below 20 or not a multiple of 4; IPv6: below 40); l3_off + l3_len > arena_len
+ * (checked without wrapping); the segment is shorter than 20 bytes; the data offset is below 5 or
+ * hlen larger than the segment; ops & ~VPCSUM_TCPRX_STORE or rsv != 0; skip > data_len; with STORE,
+ * data_len - skip > dst_cap or dst_off + stored > dst_len (without wrapping).  skip == data_len is
+ * legal and stores 0 bytes.  Descriptors and records 8-byte aligned, d_stored / d_out 4-byte aligned;
+ * n at most 2^28; n == 0 returns 0.  Stored ranges of one batch must not overlap each other: the
+ * caller's rule, as for the build. */
+int vpcsum_tcp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc,
+                          const vpcsum_tcprx_t* d_rx, uint32_t n, uint8_t* d_dst, uint64_t dst_len,
+                          uint32_t* d_stored, uint32_t* d_out, uint8_t* d_status, void* stream);
+/* What a device-resident caller needs between the parse and the receive: d_info[i] (16-byte aligned)
+ * from the TCP header's first 16 bytes of descriptor i, so that the host runs store()'s arithmetic
+ * on 16 bytes per segment instead of touching the frames.  The header refusals above apply (the
+ * descriptor's and the data offset's); a refused descriptor's record is all zero. */
+int vpcsum_tcp_digest_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc,
+                            uint32_t n, vpcsum_tcpinfo_t* d_info, void* stream);
+
 /* Streaming-read ceiling probe: reads `bytes` from d_buf with 16-B lanes, writes one word per
  * block into d_sink.  Used by bench.py to report a measured HBM read roof next to 8 TB/s. */
 int vpcsum_read_probe_async(const uint8_t* d_buf, uint64_t bytes, uint32_t* d_sink,
@@ -662,6 +722,20 @@ int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* ctx, vpcsum_flowtab_t* tab,
 int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* ctx, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
                                 const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* h_seg, uint32_t n,
                                 uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket);
+/* vpcsum_tcp_recv_async from host memory, in one submission: the payloads are written where they lie
+ * in h_dst, through its mapping, so h_dst must be inside a REGISTERED arena (the connections'
+ * receive buffers; an unregistered destination is refused, as in vpcsum_ctx_build_tcp_frames).  A
+ * registered h_arena (the RX umem) is read in place; any other is staged exactly as
+ * vpcsum_ctx_submit stages it (the descriptors' span, or their gathered 16-byte blocks, refused when
+ * larger than the context's max_arena_bytes), the descriptors rebased in the library's own copy.  n
+ * is at most the context's max_pkts.  At vpcsum_ctx_wait h_stored[i] (required), h_out[i] and
+ * h_status[i] (each may be NULL) hold what vpcsum_tcp_recv_async writes, and the payloads are in
+ * h_dst -- whatever the verdict: see vpcsum_tcp_recv_async.  The batch is always launched: there is
+ * no service-grid, device-group or process-wide form. */
+int vpcsum_ctx_recv_tcp_frames(vpcsum_ctx_t* ctx, const uint8_t* h_arena, uint64_t arena_len,
+                               const vpcsum_desc_t* h_desc, const vpcsum_tcprx_t* h_rx, uint32_t n,
+                               uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored, uint32_t* h_out,
+                               uint8_t* h_status, uint64_t* ticket);
 /* The egress flush of a batch holding NAT'd frames: vpcsum_ctx_submit where
  * descriptors with VPCSUM_F_PRE take their L4 sum from h_pre[i] (pre_fmt as vpcsum_pre_async;
  * entries of other descriptors are ignored) and the others are summed in full, in one submission.
@@ -833,6 +907,12 @@ int Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames(PNIEnv_vpcsum_long* env, i
 int Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
                                                 int64_t srcLen, void* hdr, int32_t nHdr, void* seg, int32_t n,
                                                 void* frameLen, void* out, void* status);
+/* VPCsum.recvTcpFrames(long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment rx, int n,
+ *                      MemorySegment dst, long dstLen, MemorySegment stored, MemorySegment out,
+ *                      MemorySegment status) -> long ticket (vpcsum_ctx_recv_tcp_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
+                                               void* rx, int32_t n, void* dst, int64_t dstLen, void* stored, void* out,
+                                               void* status);
 /* VPCsum.setService(long ctx, int idleUs) */
 int Java_io_vproxy_vpcsum_VPCsum_setService(PNIEnv_vpcsum_void* env, int64_t ctx, int32_t idleUs);
 /* VPCsum.waitFor(long ctx, long ticket) */

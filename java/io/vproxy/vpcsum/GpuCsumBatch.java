@@ -416,6 +416,25 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * The data segments the userspace TCP stack receives (TcpStack.handleTcpEstablished ->
+     * receivingQueue.store): {@code count} frames of the umem described in {@code frameDesc} (the
+     * parse's descriptors), one record each in {@code rx} ({@link VPCsum#tcpRx}: for a PSH segment
+     * store() keeps, dstOff the connection's receive buffer at expectingSeq and skip = expectingSeq -
+     * seq; verify only for the others), verified and stored into {@code recvBuf} -- a registered
+     * arena -- in one pass.  Replaces {@link #verify} for these frames.  Fills {@code storedOut}
+     * (u32 per record) and {@code statusOut}; the caller advances expectingSeq by storedOut[i] only
+     * when statusOut[i] has S_L4_OK: the bytes are stored whatever the verdict, and the next batch
+     * overwrites what was not accepted.
+     */
+    public MemorySegment recvTcp(MemorySegment frameDesc, MemorySegment rx, int count, MemorySegment recvBuf, long recvBufLen,
+                                 MemorySegment storedOut, MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().recvTcpFrames(env, ctx, umem, umemLen, frameDesc, rx, count, recvBuf, recvBufLen, storedOut,
+            MemorySegment.NULL, statusOut);
+        VPCsum.get().waitFor(env, ctx, t);
+        return storedOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

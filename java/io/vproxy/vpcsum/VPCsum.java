@@ -179,6 +179,53 @@ public class VPCsum {
         seg.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 31, (byte) 0);
     }
 
+    /** bytes of one vpcsum_tcprx_t receive record ({@link #tcpRx}) */
+    public static final int TCP_RX = 16;
+    /** bytes of one vpcsum_tcpinfo_t segment digest ({@link #tcpInfoSeq} and its neighbours) */
+    public static final int TCP_INFO = 16;
+    /** vpcsum_tcprx_t.ops: store the payload past {@code skip}; 0: verify only */
+    public static final int TCPRX_STORE = 0x01;
+
+    /** Fill the 16-byte receive record at {@code rx[off..]} for one received segment: payload byte
+     * {@code skip} (ReceivingQueue.store's incr = expectingSeq - seqBeginInclusive, 0 for a segment that
+     * begins on expectingSeq) goes to {@code dstOff} of the receive arena, which has room {@code dstCap}
+     * there; {@code store} false: verify only (a pure ACK, or a segment store() would drop). */
+    public static void tcpRx(MemorySegment rx, long off, long dstOff, int dstCap, int skip, boolean store) {
+        final var LE = java.nio.ByteOrder.LITTLE_ENDIAN;
+        rx.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off, dstOff);
+        rx.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 8, dstCap);
+        rx.set(java.lang.foreign.ValueLayout.JAVA_SHORT_UNALIGNED.withOrder(LE), off + 12, (short) skip);
+        rx.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 14, (byte) (store ? TCPRX_STORE : 0));
+        rx.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 15, (byte) 0);
+    }
+
+    /** Fields of the 16-byte digest at {@code info[off..]} (vpcsum_tcp_digest_async): seq and ack as
+     * TcpPacket.getSeqNum / getAckNum return them (unsigned, in a long), window, payload length,
+     * header length (0: no record, the descriptor was refused) and flags. */
+    public static long tcpInfoSeq(MemorySegment info, long off) {
+        return info.get(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(java.nio.ByteOrder.LITTLE_ENDIAN), off) & 0xffffffffL;
+    }
+
+    public static long tcpInfoAck(MemorySegment info, long off) {
+        return info.get(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(java.nio.ByteOrder.LITTLE_ENDIAN), off + 4) & 0xffffffffL;
+    }
+
+    public static int tcpInfoWindow(MemorySegment info, long off) {
+        return info.get(java.lang.foreign.ValueLayout.JAVA_SHORT_UNALIGNED.withOrder(java.nio.ByteOrder.LITTLE_ENDIAN), off + 8) & 0xffff;
+    }
+
+    public static int tcpInfoDataLen(MemorySegment info, long off) {
+        return info.get(java.lang.foreign.ValueLayout.JAVA_SHORT_UNALIGNED.withOrder(java.nio.ByteOrder.LITTLE_ENDIAN), off + 10) & 0xffff;
+    }
+
+    public static int tcpInfoHlen(MemorySegment info, long off) {
+        return info.get(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 12) & 0xff;
+    }
+
+    public static int tcpInfoFlags(MemorySegment info, long off) {
+        return info.get(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 13) & 0xff;
+    }
+
     private static final MethodHandle createMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
         "Java_io_vproxy_vpcsum_VPCsum_create", int.class /* device */, long.class /* maxArena */, int.class /* maxPkts */);
 
@@ -614,6 +661,37 @@ public class VPCsum {
         try {
             ERR = (int) buildTcpFramesMH.invokeExact(ENV.MEMORY, ctx, dst, dstLen, src, srcLen, hdr, nHdr, seg, n, frameLen, out,
                 status);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    private static final MethodHandle recvTcpFramesMH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+        "Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames", long.class /* ctx */, MemorySegment.class /* arena */, long.class /* arenaLen */,
+        MemorySegment.class /* desc */, MemorySegment.class /* rx */, int.class /* n */, MemorySegment.class /* dst */,
+        long.class /* dstLen */, MemorySegment.class /* stored */, MemorySegment.class /* out */, MemorySegment.class /* status */);
+
+    /** The TCP receive (vpcsum_ctx_recv_tcp_frames): {@code n} descriptors of received frames in
+     * {@code arena} (read in place when registered, staged otherwise), each with a record of
+     * {@link #TCP_RX} bytes ({@link #tcpRx}); every segment's TCP sum (and IPv4 header sum) is verified
+     * as {@link #verifyFrames} would and, in the same pass, its payload past {@code skip} stored at its
+     * dstOff of {@code dst}, which must lie in a registered arena (the receive buffers).  This call
+     * replaces the verify of these frames.  After {@link #waitFor}: stored[i] (u32) the bytes stored,
+     * status[i] the verify status or S_BAD_DESC for a refused record (nothing written); out / status
+     * may be MemorySegment.NULL.  THE BYTES ARE STORED WHATEVER THE VERDICT: advance expectingSeq only
+     * on S_L4_OK. */
+    public long recvTcpFrames(PNIEnv ENV, long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment rx, int n,
+                              MemorySegment dst, long dstLen, MemorySegment stored, MemorySegment out, MemorySegment status)
+        throws java.io.IOException {
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) recvTcpFramesMH.invokeExact(ENV.MEMORY, ctx, arena, arenaLen, desc, rx, n, dst, dstLen, stored, out, status);
         } catch (Throwable THROWABLE) {
             throw PanamaUtils.convertInvokeExactException(THROWABLE);
         }

@@ -1,0 +1,140 @@
+"""The TCP receive, device-resident: N received Ethernet / IPv4 / TCP frames in 2,048-byte chunks at
+chunk + 384 (umem geometry), payloads of 1,360 bytes (TcpEntry.SND_DEFAULT_MSS) and of 1,460 bytes,
+verified and stored back to back into per-connection runs of a receive buffer.  The frames are built
+on the device (vpcsum_tcp_build_async) and parsed once (vpcsum_parse_ether_async) outside the timed
+window.  Timed with events over --launches launches after a warm-up, legs in alternating rounds
+(tools/segbench.py's protocol):
+  r  vpcsum_tcp_recv_async (k_tcp_recv): the verify and the payload store in one pass
+  a  vpcsum_compute_async with MODE_VERIFY over the same descriptors: the ingress verify alone, which
+     writes nothing but out / status
+  b  a, then a hipMemcpy2DAsync of the payloads out of the chunks: what a device caller does without
+     the receive, from the entry points that existed before it (every payload byte read twice)
+  c  for scale, a contiguous device copy of the same payload bytes
+a, b and c use only entry points and kernels that this tool's library shares with its parent.
+Algorithmic bytes per frame: the segment read + data_len written + descriptor and record.  Before
+timing, r's receive buffer is compared with b's and with the send buffer, r's status and out with a's.
+Prints one JSON line.  usage: recvbench.py [frames] [--launches N]"""
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vproxy_amd import vpcsum as V  # noqa: E402
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 1 << 17
+launches = int(sys.argv[sys.argv.index("--launches") + 1]) if "--launches" in sys.argv else 50
+rounds = 3
+STRIDE, HEADROOM, HLEN = 2048, 384, 54
+
+V.lib()
+hip = None
+with open("/proc/self/maps") as f:
+    for line in f:
+        if "libamdhip64.so" in line:
+            hip = ctypes.CDLL(line.split()[-1])
+            break
+assert hip is not None, "libamdhip64 is not loaded"
+hip.hipMemcpy2DAsync.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                 ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+hip.hipMemcpy2DAsync.restype = ctypes.c_int
+D2D = 3   # hipMemcpyDeviceToDevice
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).pin_memory().cuda()
+
+
+def timed(fn):
+    for _ in range(3):
+        fn()
+    e0, e1 = V.Event(), V.Event()
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_ms(e1) / launches * 1e3   # us per launch
+
+
+hdr = np.zeros(1, V.TCPHDR_DTYPE)
+hdr["eth_dst"], hdr["eth_src"] = np.frombuffer(bytes.fromhex("02aa00000001"), np.uint8), np.frombuffer(bytes.fromhex("02bb00000002"), np.uint8)
+hdr["l2_len"], hdr["l3_ver"], hdr["ttl"] = 14, 4, 64
+hdr["src"][0, :4], hdr["dst"][0, :4] = (10, 0, 0, 1), (10, 0, 0, 2)
+hdr["sport"], hdr["dport"] = np.frombuffer((43210).to_bytes(2, "big"), np.uint8), np.frombuffer((443).to_bytes(2, "big"), np.uint8)
+hdr["ack"], hdr["window"] = np.frombuffer((0x01020304).to_bytes(4, "big"), np.uint8), np.frombuffer((65535).to_bytes(2, "big"), np.uint8)
+d_hdr = dev(hdr)
+
+res = {"frames_per_batch": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
+       "frames": "Ethernet / IPv4 / TCP, PSH|ACK, no options"}
+for data_len in (1360, 1460):
+    L = HLEN + data_len
+    seg = np.zeros(n, V.TCPSEG_DTYPE)
+    seg["frame_off"] = np.arange(n, dtype=np.uint64) * STRIDE + HEADROOM
+    seg["data_off"] = np.arange(n, dtype=np.uint64) * data_len
+    seg["seq"] = (np.arange(n, dtype=np.uint64) * data_len & 0xffffffff).astype(np.uint32)
+    seg["frame_cap"], seg["data_len"], seg["flags"] = STRIDE - HEADROOM, data_len, 0x18
+    g = torch.Generator(device="cuda").manual_seed(data_len)
+    sent = torch.randint(0, 256, (n * data_len,), dtype=torch.uint8, device="cuda", generator=g)
+    frames = torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda")
+    flen = torch.zeros(n, dtype=torch.int32, device="cuda")
+    V.tcp_build(frames, sent, d_hdr, 1, dev(seg), n, flen, None, None)
+    desc = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+    V.parse_ether(frames, dev(seg["frame_off"].copy()), flen, n, desc)
+    rx = np.zeros(n, V.TCPRX_DTYPE)
+    rx["dst_off"] = np.arange(n, dtype=np.uint64) * data_len   # runs of consecutive segments, back to back
+    rx["dst_cap"], rx["ops"] = data_len, V.TCPRX_STORE
+    d_rx = dev(rx)
+    rbuf = torch.zeros(n * data_len, dtype=torch.uint8, device="cuda")
+    stored = torch.zeros(n, dtype=torch.int32, device="cuda")
+    out_r = torch.zeros(n, dtype=torch.int32, device="cuda")
+    st_r = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    out_a = torch.zeros(n, dtype=torch.int32, device="cuda")
+    st_a = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    flat = torch.zeros(n * data_len, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def leg_r():
+        V.tcp_recv(frames, desc, d_rx, n, rbuf, stored, out_r, st_r)
+
+    def leg_a():
+        V.compute(frames, desc, n, out_a, st_a, V.MODE_VERIFY)
+
+    def leg_b():
+        leg_a()
+        rc = hip.hipMemcpy2DAsync(flat.data_ptr(), data_len, frames.data_ptr() + HEADROOM + HLEN, STRIDE, data_len, n, D2D, stream)
+        assert rc == 0, rc
+
+    copy = torch.empty_like(sent)
+
+    def leg_c():
+        copy.copy_(sent)
+
+    leg_r()
+    leg_b()
+    torch.cuda.synchronize()
+    want = V.S_DONE | V.S_IP_OK | V.S_L4_OK
+    assert int((st_r != want).sum().item()) == 0 and int((stored != data_len).sum().item()) == 0
+    assert torch.equal(st_r, st_a) and torch.equal(out_r, out_a), "r reports a's verdicts"
+    assert torch.equal(rbuf, sent) and torch.equal(flat, sent), "r and b store the sent bytes"
+    legs = {"r_tcp_recv": leg_r, "a_compute_verify": leg_a, "b_verify_plus_copy2d": leg_b, "c_contiguous_copy": leg_c}
+    us = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            us[k].append(round(timed(fn), 2))
+    assert torch.equal(rbuf, sent)
+    bytes_per_frame = (L - 14 - 20) + data_len + 32
+    r = {"frame_len": L, "algorithmic_bytes_per_frame": bytes_per_frame}
+    for k, v in us.items():
+        med = sorted(v)[len(v) // 2]
+        r[k] = {"us_rounds": v, "us_median": med, "Mframes_per_s": round(n / med, 2), "GB_per_s": round(n * bytes_per_frame / med / 1e3, 1)}
+    r["c_contiguous_copy"]["GB_per_s"] = round(n * 2 * data_len / r["c_contiguous_copy"]["us_median"] / 1e3, 1)   # its own bytes
+    r["r_over_a"] = round(r["r_tcp_recv"]["us_median"] / r["a_compute_verify"]["us_median"], 3)
+    r["b_over_r"] = round(r["b_verify_plus_copy2d"]["us_median"] / r["r_tcp_recv"]["us_median"], 3)
+    r["r_over_c"] = round(r["r_tcp_recv"]["us_median"] / r["c_contiguous_copy"]["us_median"], 3)
+    res[f"data_len_{data_len}"] = r
+    del sent, frames, rbuf, flat, copy
+print(json.dumps(res))

@@ -26,6 +26,7 @@
 #include "flow_table.h"
 #include "internal.h"
 #include "tcp_build.h"
+#include "tcp_recv.h"
 #include "vpcsum.h"
 
 namespace vpcsum {
@@ -201,7 +202,8 @@ struct Slot {
     Mapped<uint32_t> h_port;           // and its output ports
     Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records, templates and frame lengths
     Mapped<vpcsum_tcphdr_t> h_thdr;
-    Mapped<uint32_t> h_tlen;
+    Mapped<uint32_t> h_tlen;           // (a TCP receive batch's stored counts too)
+    Mapped<vpcsum_tcprx_t> h_trx;      // a TCP receive batch's records
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool busy = false;                 // `batch` is in flight
@@ -1200,6 +1202,35 @@ static int desc_entry(vpcsum_ctx* c, uint8_t* h_arena, uint64_t arena_len, const
     return body(*s, b, sp, dev_arena ? dev_arena - sp.lo : nullptr);
 }
 
+// The frames of a staged descriptor batch (batch_plan.h), into the slot's pinned staging: a sparse
+// batch in a large pageable arena as its gathered 16-B blocks, any other as the span [lo, hi).
+// s.h_desc holds the descriptors rebased to the staging (out of the span: UINT64_MAX, refused by the
+// kernels); *dev_len is how many bytes stage_frames_up carries.
+static int stage_desc_frames(vpcsum_ctx* c, Slot& s, const char* what, const uint8_t* h_arena, uint64_t arena_len,
+                             const vpcsum_desc_t* h_desc, uint32_t n, const BatchSpan& sp, uint64_t* dev_len) {
+    const uint64_t lo = sp.lo, span = sp.hi - sp.lo;
+    if (span > 2 * sp.used + (64u << 10)) {
+        // sparse batch in a large pageable arena: gather the touched 16-B blocks only
+        const int64_t staged = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena.p, c->max_arena);
+        if (staged < 0) return fail("%s: gathered batch exceeds capacity", what);
+        *dev_len = (uint64_t)staged;
+        return 0;
+    }
+    if (span > c->max_arena)
+        return fail("%s: batch spans %llu bytes > capacity %llu", what, (unsigned long long)span, (unsigned long long)c->max_arena);
+    // descriptors rebased to the device copy of [lo, hi)
+    for (uint32_t i = 0; i < n; ++i) {
+        s.h_desc.p[i] = h_desc[i];
+        if (h_desc[i].l3_off >= lo) s.h_desc.p[i].l3_off = h_desc[i].l3_off - lo;
+        else s.h_desc.p[i].l3_off = UINT64_MAX;   // out of span -> BAD in the kernel
+    }
+    // through the pinned staging, always: the span lies in no arena this context registered, and the
+    // library never DMAs from memory it did not register (is_registered)
+    if (span) memcpy(s.h_arena.p, h_arena + lo, span);
+    *dev_len = span;
+    return 0;
+}
+
 extern "C" {
 
 int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc, uint32_t n,
@@ -1208,7 +1239,6 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
         if (desc_args(c, "vpcsum_ctx_submit", "arena or descriptors", h_arena, h_desc, h_desc, n, ticket) != 0) return -1;
         if (mode & ~(VPCSUM_MODE_VERIFY | VPCSUM_MODE_WRITE)) return fail("vpcsum_ctx_submit: bad mode 0x%x", mode);
         return desc_entry(c, h_arena, arena_len, h_desc, n, mode, [&](Slot& s, Batch& b, const BatchSpan& sp, uint8_t* base) {
-            const uint64_t lo = sp.lo, span = sp.hi - sp.lo;
             const bool svc = base && c->svc.on && n <= kSvcBatchMax;
             b.hand_back({status_of(c, s, svc, h_status, n), out_of(c, s, svc, h_out, n)});
             if (base) {
@@ -1226,26 +1256,8 @@ int vpcsum_ctx_submit(vpcsum_ctx_t* c, uint8_t* h_arena, uint64_t arena_len, con
                           "checksum launch (zero-copy)");
                 b.zero_copy = true;
             } else {
-                const bool gather = span > 2 * sp.used + (64u << 10);
-                uint64_t dev_len = span;
-                if (gather) {
-                    // sparse batch in a large pageable arena: gather the touched 16-B blocks only
-                    const int64_t staged = gather_blocks(h_arena, arena_len, h_desc, n, s.h_desc.p, s.h_arena.p, c->max_arena);
-                    if (staged < 0) return fail("vpcsum_ctx_submit: gathered batch exceeds capacity");
-                    dev_len = (uint64_t)staged;
-                } else {
-                    if (span > c->max_arena) return fail("vpcsum_ctx_submit: batch spans %llu bytes > capacity %llu",
-                                                         (unsigned long long)span, (unsigned long long)c->max_arena);
-                    // descriptors rebased to the device copy of [lo, hi)
-                    for (uint32_t i = 0; i < n; ++i) {
-                        s.h_desc.p[i] = h_desc[i];
-                        if (h_desc[i].l3_off >= lo) s.h_desc.p[i].l3_off = h_desc[i].l3_off - lo;
-                        else s.h_desc.p[i].l3_off = UINT64_MAX;   // out of span -> BAD in the kernel
-                    }
-                }
-                // through the pinned staging, always: the span lies in no arena this context registered
-                // (base is NULL), and the library never DMAs from memory it did not register (is_registered)
-                if (!gather && span) memcpy(s.h_arena.p, h_arena + lo, span);
+                uint64_t dev_len = 0;
+                if (stage_desc_frames(c, s, "vpcsum_ctx_submit", h_arena, arena_len, h_desc, n, sp, &dev_len) != 0) return -1;
                 if (stage_up(s, n, 0, dev_len) != 0) return -1;
                 // the out words travel when the caller asked for them or MODE_WRITE places them in the frames
                 const bool want_out = h_out || (mode & VPCSUM_MODE_WRITE);
@@ -1781,6 +1793,39 @@ int vpcsum_tcp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_sr
     } VPC_CATCH("vpcsum_tcp_build_async")
 }
 
+int vpcsum_tcp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, const vpcsum_tcprx_t* d_rx,
+                          uint32_t n, uint8_t* d_dst, uint64_t dst_len, uint32_t* d_stored, uint32_t* d_out, uint8_t* d_status,
+                          void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_arena && arena_len) return fail("vpcsum_tcp_recv_async: NULL arena");
+        if (!d_desc || !d_rx) return fail("vpcsum_tcp_recv_async: NULL descriptors or records");
+        if (!d_dst && dst_len) return fail("vpcsum_tcp_recv_async: NULL destination arena");
+        if (!d_stored) return fail("vpcsum_tcp_recv_async: NULL stored counts");
+        if (((uintptr_t)d_desc | (uintptr_t)d_rx) & 7) return fail("vpcsum_tcp_recv_async: descriptors or records not 8-byte aligned");
+        if ((uintptr_t)d_stored & 3) return fail("vpcsum_tcp_recv_async: stored counts not 4-byte aligned");
+        if ((uintptr_t)d_out & 3) return fail("vpcsum_tcp_recv_async: out words not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_tcp_recv_async: %u records > 2^28", n);
+        VPC_CHECK(launch_tcp_recv(d_arena, arena_len, d_desc, d_rx, n, d_dst, dst_len, d_stored, d_out, d_status,
+                                  (hipStream_t)stream),
+                  "TCP receive launch");
+        return 0;
+    } VPC_CATCH("vpcsum_tcp_recv_async")
+}
+
+int vpcsum_tcp_digest_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, uint32_t n,
+                            vpcsum_tcpinfo_t* d_info, void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_arena && arena_len) return fail("vpcsum_tcp_digest_async: NULL arena");
+        if (!d_desc || !d_info) return fail("vpcsum_tcp_digest_async: NULL descriptors or records");
+        if ((uintptr_t)d_desc & 7) return fail("vpcsum_tcp_digest_async: descriptors not 8-byte aligned");
+        if ((uintptr_t)d_info & 15) return fail("vpcsum_tcp_digest_async: records not 16-byte aligned");
+        VPC_CHECK(launch_tcp_digest(d_arena, arena_len, d_desc, n, d_info, (hipStream_t)stream), "TCP digest launch");
+        return 0;
+    } VPC_CATCH("vpcsum_tcp_digest_async")
+}
+
 int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream) {
     try {
         if (!f || !n_out) return fail("vpcsum_flowtab_collect: NULL table or count");
@@ -1909,6 +1954,43 @@ int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_le
         }
         return slot_commit(s, b, ticket);
     } VPC_CATCH("vpcsum_ctx_build_tcp_frames")
+}
+
+// The TCP receive of host memory: payloads written in place into a registered destination, the
+// frames read in place from a registered arena or staged by vpcsum_ctx_submit's plan.  Always
+// launched, on the slot's one stream; descriptors, records and results in mapped pinned memory.
+int vpcsum_ctx_recv_tcp_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc,
+                               const vpcsum_tcprx_t* h_rx, uint32_t n, uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored,
+                               uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
+    const char* what = "vpcsum_ctx_recv_tcp_frames";
+    try {
+        if (desc_args(c, what, "arena, descriptors or records", h_arena, h_desc, h_rx, n, ticket) != 0) return -1;
+        if (n && (!h_stored || (!h_dst && dst_len))) return fail("%s: NULL destination or stored counts", what);
+        return desc_entry(c, const_cast<uint8_t*>(h_arena), arena_len, h_desc, n, VPCSUM_MODE_VERIFY,
+                          [&](Slot& s, Batch& b, const BatchSpan& sp, uint8_t* base) {
+            uint8_t* dst_dev = n && dst_len ? mapped_dev(c, h_dst, dst_len) : nullptr;
+            if (n && dst_len && !dst_dev) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
+            b.user_arena = nullptr;   // nothing goes back into the frames
+            b.user_desc = nullptr;
+            b.zero_copy = true;       // the payloads are written in place through the destination's mapping
+            if (n) {
+                if (slot_scratch(c, what, s.h_trx, s.h_tlen) != 0) return -1;
+                b.hand_back({status_of(c, s, false, h_status, n), {h_stored, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
+                memcpy(s.h_trx.p, h_rx, (size_t)n * sizeof(vpcsum_tcprx_t));
+                uint64_t dev_len = arena_len;
+                if (base) {
+                    memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+                } else {
+                    if (stage_desc_frames(c, s, what, h_arena, arena_len, h_desc, n, sp, &dev_len) != 0) return -1;
+                    if (stage_frames_up(s, dev_len) != 0) return -1;
+                }
+                VPC_CHECK(launch_tcp_recv(base ? base : s.d_arena.p, dev_len, s.h_desc.dev, s.h_trx.dev, n, dst_dev, dst_len,
+                                          s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
+                          "TCP receive launch");
+            }
+            return slot_commit(s, b, ticket);
+        });
+    } VPC_CATCH("vpcsum_ctx_recv_tcp_frames")
 }
 
 int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint32_t copy_bytes,
@@ -2576,6 +2658,17 @@ int Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames(PNIEnv_vpcsum_long* env, int64_t
                                            (uint64_t)srcLen, (const vpcsum_tcphdr_t*)hdr, (uint32_t)nHdr,
                                            (const vpcsum_tcpseg_t*)seg, (uint32_t)n, (uint32_t*)frameLen, (uint32_t*)out,
                                            (uint8_t*)status, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
+                                               void* rx, int32_t n, void* dst, int64_t dstLen, void* stored, void* out,
+                                               void* status) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames", n < 0 || arenaLen < 0 || dstLen < 0,
+                         "recvTcpFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_recv_tcp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
+                                          (const vpcsum_desc_t*)desc, (const vpcsum_tcprx_t*)rx, (uint32_t)n, (uint8_t*)dst,
+                                          (uint64_t)dstLen, (uint32_t*)stored, (uint32_t*)out, (uint8_t*)status, t);
     });
 }
 

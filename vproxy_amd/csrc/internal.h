@@ -115,6 +115,16 @@ hipError_t launch_tcp_build(uint8_t* dst, uint64_t dst_len, const uint8_t* src, 
                             const vpcsum_tcphdr_t* hdrs, uint32_t n_hdr, const vpcsum_tcpseg_t* segs, uint32_t n,
                             uint32_t* frame_len_out, uint32_t* out, uint8_t* status, hipStream_t stream);
 
+// TCP receive (tcp_recv.hip, vpcsum.h vpcsum_tcp_recv_async's rule): descriptor i verified as
+// VPCSUM_MODE_VERIFY does and, under rx[i], its payload past `skip` stored at dst + rx[i].dst_off;
+// stored[i] = the byte count, 0 for a refused record; out / status may be NULL.  k_tcp_digest: info[i]
+// from the TCP header's first 16 bytes, all zero for a refused descriptor.
+hipError_t launch_tcp_recv(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const vpcsum_tcprx_t* rx,
+                           uint32_t n, uint8_t* dst, uint64_t dst_len, uint32_t* stored, uint32_t* out, uint8_t* status,
+                           hipStream_t stream);
+hipError_t launch_tcp_digest(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, uint32_t n,
+                             vpcsum_tcpinfo_t* info, hipStream_t stream);
+
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t grid, hipStream_t stream);
 hipError_t launch_pattern_probe(const uint8_t* arena, uint64_t arena_len, const void* desc, uint32_t n, uint32_t* sink,
                                 uint32_t grid, hipStream_t stream);

@@ -60,6 +60,14 @@ TCPHDR_DTYPE = np.dtype([("eth_dst", "u1", 6), ("eth_src", "u1", 6), ("l2_len", 
 # order), template index, the room at frame_off, payload length, TCP flags
 TCPSEG_DTYPE = np.dtype([("frame_off", "<u8"), ("data_off", "<u8"), ("seq", "<u4"), ("hdr", "<u4"), ("frame_cap", "<u4"),
                          ("data_len", "<u2"), ("flags", "u1"), ("rsv", "u1")])
+# vpcsum_tcprx_t (16 B): what the TCP receive does with descriptor i -- where payload byte `skip`
+# goes in the receive arena, the room there, the bytes already received, TCPRX_STORE or 0 (verify only)
+TCPRX_DTYPE = np.dtype([("dst_off", "<u8"), ("dst_cap", "<u4"), ("skip", "<u2"), ("ops", "u1"), ("rsv", "u1")])
+TCPRX_STORE = 0x01
+# vpcsum_tcpinfo_t (16 B): a segment's seq, ack, window, payload length (host order), header length
+# and flags; hlen 0: no record (a refused descriptor), the rest 0
+TCPINFO_DTYPE = np.dtype([("seq", "<u4"), ("ack", "<u4"), ("window", "<u2"), ("data_len", "<u2"), ("hlen", "u1"),
+                          ("flags", "u1"), ("rsv", "u1", 2)])
 
 # Every symbol include/vpcsum.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -95,7 +103,12 @@ EXPORTS = [
     "vpcsum_ctx_nat_flow_forward_frames", "Java_io_vproxy_vpcsum_VPCsum_flowtabSetFastpath",
     "Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames",
     "vpcsum_tcp_build_async", "vpcsum_ctx_build_tcp_frames", "Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames",
+    "vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames",
+    "Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames",
 ]
+
+# additive entry points this binding probes for instead of requiring (see _declare)
+_PROBED = ("vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames")
 
 
 class VpcsumUnavailable(RuntimeError):
@@ -273,8 +286,17 @@ def _declare(L):
         "vpcsum_ctx_nat_flow_forward_frames": ([P, P, P, U64, P, P, U32, P, P, P, U32, P], I),
         "vpcsum_tcp_build_async": ([P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
         "vpcsum_ctx_build_tcp_frames": ([P, P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
+        "vpcsum_tcp_recv_async": ([P, U64, P, P, U32, P, U64, P, P, P, P], I),
+        "vpcsum_tcp_digest_async": ([P, U64, P, U32, P, P], I),
+        "vpcsum_ctx_recv_tcp_frames": ([P, P, U64, P, P, U32, P, U64, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
+        # The TCP receive came after ABI version 4 was fixed: a caller probes for it by looking the
+        # symbols up (include/vpcsum.h).  So does this binding -- it loads a library from before them
+        # (tools/ab_libs.sh compares against one), and using tcp_recv() on such a library raises
+        # ctypes' "undefined symbol", never a fallback.
+        if name in _PROBED and not hasattr(L, name):
+            continue
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res
@@ -535,6 +557,29 @@ def tcp_build(dst, src, hdrs, n_hdr: int, segs, n: int, frame_len, out=None, sta
     _check(lib().vpcsum_tcp_build_async(_ptr(dst), dst.numel() * dst.element_size(), _ptr(src),
                                         src.numel() * src.element_size(), _ptr(hdrs), n_hdr, _ptr(segs), n, _ptr(frame_len),
                                         _ptr(out), _ptr(status), _stream(stream)), "vpcsum_tcp_build_async")
+
+
+def tcp_recv(arena, desc, rx, n: int, dst, stored, out=None, status=None, stream=None):
+    """vpcsum_tcp_recv_async on device tensors: `arena` the received frames, `desc` n x 16 bytes (the
+    parse's descriptors), `rx` n x 16 bytes (TCPRX_DTYPE), `dst` the uint8 receive arena, `stored`
+    n x uint32 (written: the bytes stored, 0 for a refused or verify-only record), `out` n x uint32 and
+    `status` n bytes (each may be None; what compute() writes with MODE_VERIFY).  The payload bytes
+    are stored whatever the verdict: accept them on S_L4_OK only."""
+    assert desc.numel() * desc.element_size() >= n * 16 and rx.numel() * rx.element_size() >= n * TCPRX_DTYPE.itemsize
+    assert stored.numel() * stored.element_size() >= n * 4
+    assert out is None or out.numel() * out.element_size() >= n * 4
+    assert status is None or status.numel() >= n
+    _check(lib().vpcsum_tcp_recv_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(desc), _ptr(rx), n, _ptr(dst),
+                                       dst.numel() * dst.element_size(), _ptr(stored), _ptr(out), _ptr(status),
+                                       _stream(stream)), "vpcsum_tcp_recv_async")
+
+
+def tcp_digest(arena, desc, n: int, info, stream=None):
+    """vpcsum_tcp_digest_async on device tensors: `info` n x 16 bytes (TCPINFO_DTYPE, 16-byte aligned),
+    written from the TCP header's first 16 bytes of each descriptor; all zero for a refused one."""
+    assert desc.numel() * desc.element_size() >= n * 16 and info.numel() * info.element_size() >= n * TCPINFO_DTYPE.itemsize
+    _check(lib().vpcsum_tcp_digest_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(desc), n, _ptr(info),
+                                         _stream(stream)), "vpcsum_tcp_digest_async")
 
 
 class FlowTable:
@@ -815,6 +860,29 @@ class Context:
                "vpcsum_ctx_build_tcp_frames")
         self.wait(t.value)
         return frame_len, out, status
+
+    def recv_tcp_frames(self, arena: np.ndarray, desc: np.ndarray, rx: np.ndarray, dst: np.ndarray, want_out: bool = True,
+                        want_status: bool = True):
+        """vpcsum_ctx_recv_tcp_frames: descriptor i of `arena` verified and, under rx[i] (TCPRX_DTYPE),
+        its payload stored into `dst`, which must lie in a registered arena; a registered `arena` is
+        read in place, any other staged as submit() stages it.  Returns (stored, out, status) per
+        record (out / status None when not asked for).  Stored whatever the verdict: accept a
+        segment's bytes on S_L4_OK only."""
+        assert desc.dtype == DESC_DTYPE and rx.dtype == TCPRX_DTYPE and len(desc) == len(rx)
+        n = len(desc)
+        ds, rr = np.ascontiguousarray(desc), np.ascontiguousarray(rx)
+        stored = np.zeros(n, np.uint32)
+        out = np.zeros(n, np.uint32) if want_out else None
+        status = np.zeros(n, np.uint8) if want_status else None
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_recv_tcp_frames(self.h, arena.ctypes.data, arena.nbytes, ds.ctypes.data if n else None,
+                                                rr.ctypes.data if n else None, n, dst.ctypes.data if dst.nbytes else None,
+                                                dst.nbytes, stored.ctypes.data,
+                                                None if out is None else out.ctypes.data,
+                                                None if status is None else status.ctypes.data, ctypes.byref(t)),
+               "vpcsum_ctx_recv_tcp_frames")
+        self.wait(t.value)
+        return stored, out, status
 
     def set_service(self, idle_us: int):
         """Low-latency flushes from registered arenas (persistent service grid); 0 = off."""

@@ -12,6 +12,8 @@ callers).  Same contract as java/io/vproxy/vpcsum/GpuCsumBatch.java:
   (EthernetPacket/Ipv4Packet/Ipv6Packet.from rules) for ingress verify.
 * :func:`recalc_policy` -- the verify status -> DevInput csum-recalc decision (which frames get
   their sums marked dirty, which are dropped), INTEGRATION.md §4.
+* :func:`plan_tcp_store` -- TcpEntry.ReceivingQueue.store's decision on plain integers: the `skip`
+  of a vpcsum_tcprx_t record, or "not stored" (a verify-only record).
 
 No checksum is computed on the CPU here: everything goes through libvpcsum.so.
 """
@@ -532,6 +534,25 @@ def recalc_policy(status: np.ndarray, desc: np.ndarray, csum_recalc: str = CSUM_
              "rx_dropped": int(np.count_nonzero(drop)),
              "rx_marked_dirty": int(np.count_nonzero(ip_dirty | l4_dirty))}
     return RecalcDecision(ip_dirty, l4_dirty, drop, stats)
+
+
+def plan_tcp_store(expecting_seq: int, seq: int, data_len: int):
+    """What ReceivingQueue.store (TcpEntry.java:390-426) does with a segment [seq, seq + data_len)
+    when the connection expects `expecting_seq`: ``(skip, stored)`` -- the record's `skip` (store()'s
+    incr) and the bytes the receive buffer gains, written at the buffer's `expecting_seq` -- or None
+    when store() keeps nothing (a verify-only record).  The four branches, in its order: a segment
+    that begins past the expected byte is dropped (no reordering); one that ends at or before it was
+    already received; one that begins before it is trimmed by ``expecting_seq - seq``; one that
+    begins on it is taken whole.  remoteClosed, RMEM_MAX, the window and the readable() callback stay
+    the host's; sequence numbers are the stack's longs (no wrap here either)."""
+    if seq > expecting_seq:
+        return None
+    if seq + data_len <= expecting_seq:
+        return None
+    if seq < expecting_seq:
+        skip = expecting_seq - seq
+        return skip, data_len - skip
+    return 0, data_len
 
 
 def verify_frames(ctx: "V.Context", arena: np.ndarray, desc: np.ndarray):
