@@ -1,12 +1,14 @@
 """CPU-side checks of the TCP segment build (vpcsum_tcp_build_async, vpcsum_ctx_build_tcp_frames,
 VPCsum.buildTcpFrames): the Python restatement of the frame rule (tests/tcpbuildvec.py) against the
-reference's own test frame and the oracle's parser, the host-checkable rules of tcp_build.h in a
-stand-alone program under ASan / UBSan, the layouts the binding, the header and the kernel share,
-the kernel's budget read from the code object, and the argument refusals that need no device."""
+reference's own test frame and the oracle's parser, the host-checkable rules of tcp_build.h and the
+payload mover of team_move.h in stand-alone programs under ASan / UBSan, the layouts the binding,
+the header and the kernel share, the kernel's budget read from the code object, and the argument
+refusals that need no device."""
 import ctypes
 import json
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -128,6 +130,26 @@ def test_tcp_build_rules_under_sanitizers(tmp_path):
     r = subprocess.run([str(exe), k["hex"], str(rec["seq"]), str(rec["flags"])], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "tcp_build ok (with the reference frame)" in r.stdout, (r.returncode, r.stdout, r.stderr)
     assert "reference header 54 bytes, ip sum 85f7, tcp sum 0aa9" in r.stdout
+
+
+def test_team_move_under_sanitizers(tmp_path):
+    """tests/cpp/team_move_test.cpp: team_move.h's mover, the one k_tcp_build and k_tcp_recv run,
+    compiled for the host alone and run under ASan / UBSan over a source block that is exactly the
+    segment's 4-byte aligned hull and a destination block that ends at the last stored byte --
+    lengths 0..80 and 1,460, every destination residue mod 16 and source residue mod 4, the stored
+    range from every offset of the segment (none, inside one dword, inside one group), stored bytes
+    and the sum against a byte-wise reference."""
+    from vproxy_amd import build
+    cc = shutil.which(build.hipcc())
+    if cc is None:
+        pytest.skip("hipcc not found")
+    exe = tmp_path / "team_move_test"
+    subprocess.check_call([cc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(REPO, "include"),
+                           "-I", os.path.join(REPO, "vproxy_amd", "csrc"),
+                           os.path.join(REPO, "tests", "cpp", "team_move_test.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "team_move ok: " in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
 # ------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvpcsum.so")
 SOURCES = ["kernels.hip", "nat.hip", "flow.hip", "tcp_build.hip", "tcp_recv.hip", "api.cpp"]
 HEADERS = ["internal.h", "launch_modes.h", "batch_plan.h", "device_common.h", "pre_common.h", "tcp_rewrite.h", "flow_table.h",
-           "tcp_build.h", "tcp_recv.h", os.path.join("..", "..", "include", "vpcsum.h")]
+           "tcp_build.h", "tcp_recv.h", "team_move.h", os.path.join("..", "..", "include", "vpcsum.h")]
 ARCH = os.environ.get("VPCSUM_ARCH", "gfx950")
 
 

@@ -1,4 +1,5 @@
-// device_common.h -- device helpers shared by the kernels of libvpcsum (kernels.hip, nat.hip).
+// device_common.h -- device helpers shared by the kernels of libvpcsum (kernels.hip, nat.hip, flow.hip,
+// tcp_build.hip and tcp_recv.hip; the last three through team_move.h too).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,7 +8,7 @@
 namespace vpcsum {
 
 // Bytes of the dword at relative byte position d that fall inside [lo, hi).
-__device__ __forceinline__ uint32_t bmask(int d, int lo, int hi) {
+__host__ __device__ __forceinline__ uint32_t bmask(int d, int lo, int hi) {
     int s = min(max(lo - d, 0), 4);
     int e = min(max(hi - d, 0), 4);
     uint32_t me = e >= 4 ? 0xffffffffu : ((1u << (e << 3)) - 1u);
@@ -28,7 +29,25 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 // tools/bwlab.hip).
 // (address space 1 so hipcc emits global_load_dwordx4, not flat_load: flat loads count on
 // lgkmcnt too and force vmcnt(0)+lgkmcnt(0) waits that serialise the U loads in flight.)
-typedef __attribute__((address_space(1))) const u32x4_t gu32x4_t;
+#ifdef __HIP_DEVICE_COMPILE__
+#define VPC_GLOBAL __attribute__((address_space(1)))
+#else
+#define VPC_GLOBAL   // host builds of team_move.h: plain memory
+#endif
+typedef VPC_GLOBAL const u32x4_t gu32x4_t;
+// The other pointee types of global loads (g...) and stores (gw...); the a4 vectors are dwords at
+// 4-B alignment (tuples are 40 B apart, entries 48 B, a segment's bytes anywhere).
+typedef uint32_t u32x4a4_t __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x2a4_t __attribute__((ext_vector_type(2), aligned(4)));
+typedef VPC_GLOBAL const u32x4a4_t gu32x4a4_t;
+typedef VPC_GLOBAL const u32x2a4_t gu32x2a4_t;
+typedef VPC_GLOBAL const uint32_t gu32_t;
+typedef VPC_GLOBAL const uint8_t gu8_t;
+typedef VPC_GLOBAL u32x4_t gwu32x4_t;
+typedef VPC_GLOBAL u32x4a4_t gwu32x4a4_t;
+typedef VPC_GLOBAL uint32_t gwu32_t;
+typedef VPC_GLOBAL uint16_t gwu16_t;
+typedef VPC_GLOBAL uint8_t gwu8_t;
 template <bool NT>
 __device__ __forceinline__ uint4 ld_stream(const uint4* q) {
     const u32x4_t v = NT ? __builtin_nontemporal_load((gu32x4_t*)q) : *(gu32x4_t*)q;
@@ -52,6 +71,27 @@ __device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xff) << 
 // A sum taken over a byte range that starts at an even absolute address is byte-swapped
 // relative to the big-endian word grid of that range (RFC 1071 byte-order independence).
 __device__ __forceinline__ uint32_t orient(uint32_t v, int start) { return (start & 1) ? v : bswap16(v); }
+
+// Sum over the TEAM lanes of a team (aligned lane groups; every lane gets the total).  Teams of
+// up to 16 lanes reduce with DPP lane swizzles inside a row (xor 1, xor 2 by quad_perm, then
+// the half-row and row mirrors), one VALU op per step instead of an LDS-crossbar bpermute.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+template <int TEAM>
+__device__ __forceinline__ uint32_t team_sum(uint32_t v) {
+    if (TEAM <= 16) {
+        if (TEAM >= 2) v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
+        if (TEAM >= 4) v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
+        if (TEAM >= 8) v = dpp_add<0x141>(v);   // row_half_mirror
+        if (TEAM >= 16) v = dpp_add<0x140>(v);  // row_mirror
+        return v;
+    }
+#pragma unroll
+    for (int m = TEAM / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, TEAM);
+    return v;
+}
 
 __device__ __forceinline__ int l4_field(int proto) {
     return proto == 6 ? 16 : proto == 17 ? 6 : (proto == 1 || proto == 58) ? 2 : -1;

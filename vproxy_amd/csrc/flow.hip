@@ -21,15 +21,9 @@
 #include "device_common.h"
 #include "flow_table.h"
 #include "internal.h"
+#include "team_move.h"
 
 namespace vpcsum {
-
-// 16 B of dwords at 4-B alignment (tuples are 40 B apart, entries 48 B)
-typedef uint32_t u32x4a4_t __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u32x2a4_t __attribute__((ext_vector_type(2), aligned(4)));
-typedef __attribute__((address_space(1))) const u32x4a4_t g_u32x4a4_t;
-typedef __attribute__((address_space(1))) const u32x2a4_t g_u32x2a4_t;
-typedef __attribute__((address_space(1))) u32x4a4_t gw_u32x4a4_t;
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64);
@@ -54,10 +48,10 @@ __device__ __forceinline__ void flow_lookup_team(const FlowSlot* __restrict__ sl
     uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
     const uint8_t* tp = (const uint8_t*)(tuples + (valid ? pkt : 0u)) + l8 * 16u;
     if (valid && l8 < 2) {
-        const u32x4a4_t v = __builtin_nontemporal_load((g_u32x4a4_t*)tp);
+        const u32x4a4_t v = __builtin_nontemporal_load((gu32x4a4_t*)tp);
         t0 = v.x; t1 = v.y; t2 = v.z; t3 = v.w;
     } else if (valid && l8 == 2) {
-        const u32x2a4_t v = __builtin_nontemporal_load((g_u32x2a4_t*)tp);
+        const u32x2a4_t v = __builtin_nontemporal_load((gu32x2a4_t*)tp);
         t0 = v.x;
         t1 = v.y;
     }
@@ -104,7 +98,7 @@ __device__ __forceinline__ void flow_lookup_team(const FlowSlot* __restrict__ sl
         // the entry as loaded, or zeros (mask 0: the rewrite kernel answers S_DONE and writes nothing)
         u32x4a4_t o;
         o.x = hit ? s0 : 0u; o.y = hit ? s1 : 0u; o.z = hit ? s2 : 0u; o.w = hit ? s3 : 0u;
-        *(gw_u32x4a4_t*)((uint8_t*)(rw_out + pkt) + (l8 - 3u) * 16u) = o;
+        *(gwu32x4a4_t*)((uint8_t*)(rw_out + pkt) + (l8 - 3u) * 16u) = o;
     } else if (l8 == 2) {
         if (hit) touched[s2] = 1;   // s2: the flow id; a plain byte store of a constant, idempotent
     } else if (l8 == 0) {
@@ -113,7 +107,7 @@ __device__ __forceinline__ void flow_lookup_team(const FlowSlot* __restrict__ sl
         // the flow's Fastpath (slot bytes 112..127) as loaded, or zeros
         u32x4a4_t o;
         o.x = hit ? s0 : 0u; o.y = hit ? s1 : 0u; o.z = hit ? s2 : 0u; o.w = hit ? s3 : 0u;
-        *(gw_u32x4a4_t*)(fp_out + pkt) = o;
+        *(gwu32x4a4_t*)(fp_out + pkt) = o;
     }
 }
 
@@ -137,49 +131,8 @@ __global__ __launch_bounds__(256) void k_flowfp(const FlowSlot* __restrict__ slo
 // The L2 write (vpcsum_l2_forward_async): one lane per frame.  A frame's 12 address bytes start at
 // arena + frame_off, of any alignment; they are held as three little-endian dwords and leave in the
 // widest naturally aligned stores the address allows -- 3 stores at a 4-B aligned address, 4 at an
-// even one, 5 at an odd one -- each store's bytes cut from the dwords at compile-time positions
-// (one instantiation per address residue mod 4: no indexed register array, no scratch).
+// even one, 5 at an odd one (team_move.h store_piece_any).
 // ------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(1))) uint32_t gw32_t;
-typedef __attribute__((address_space(1))) uint16_t gw16_t;
-typedef __attribute__((address_space(1))) uint8_t gw8_t;
-
-// bytes [POS, POS + 4) of the 12 (POS <= 8; a tail store uses fewer of them)
-template <int POS>
-__device__ __forceinline__ uint32_t mac_bytes(uint32_t w0, uint32_t w1, uint32_t w2) {
-    constexpr int k = POS >> 2, sh = (POS & 3) * 8;
-    const uint32_t lo = k == 0 ? w0 : k == 1 ? w1 : w2;
-    const uint32_t hi = k == 0 ? w1 : k == 1 ? w2 : 0u;
-    return sh == 0 ? lo : (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
-}
-
-// R = address & 3
-template <int R>
-__device__ __forceinline__ void store_macs(uint8_t* p, uint32_t w0, uint32_t w1, uint32_t w2) {
-    if constexpr (R == 0) {
-        *(gw32_t*)p = w0;
-        *(gw32_t*)(p + 4) = w1;
-        *(gw32_t*)(p + 8) = w2;
-    } else if constexpr (R == 2) {
-        *(gw16_t*)p = (uint16_t)w0;
-        *(gw32_t*)(p + 2) = mac_bytes<2>(w0, w1, w2);
-        *(gw32_t*)(p + 6) = mac_bytes<6>(w0, w1, w2);
-        *(gw16_t*)(p + 10) = (uint16_t)(w2 >> 16);
-    } else if constexpr (R == 1) {   // p + 1 is 2 mod 4
-        *(gw8_t*)p = (uint8_t)w0;
-        *(gw16_t*)(p + 1) = (uint16_t)(w0 >> 8);
-        *(gw32_t*)(p + 3) = mac_bytes<3>(w0, w1, w2);
-        *(gw32_t*)(p + 7) = mac_bytes<7>(w0, w1, w2);
-        *(gw8_t*)(p + 11) = (uint8_t)(w2 >> 24);
-    } else {                         // R == 3: p + 1 is 4-B aligned
-        *(gw8_t*)p = (uint8_t)w0;
-        *(gw32_t*)(p + 1) = mac_bytes<1>(w0, w1, w2);
-        *(gw32_t*)(p + 5) = mac_bytes<5>(w0, w1, w2);
-        *(gw16_t*)(p + 9) = (uint16_t)(w2 >> 8);
-        *(gw8_t*)(p + 11) = (uint8_t)(w2 >> 24);
-    }
-}
-
 __global__ __launch_bounds__(256) void k_l2_forward(uint8_t* __restrict__ arena, uint64_t arena_len,
                                                    const uint64_t* __restrict__ frame_off,
                                                    const uint32_t* __restrict__ frame_len,
@@ -191,19 +144,13 @@ __global__ __launch_bounds__(256) void k_l2_forward(uint8_t* __restrict__ arena,
     const uint64_t off = frame_off[i];
     const uint32_t len = frame_len[i];
     const uint32_t vd = verdict[i], st = status[i];
-    const u32x4a4_t f = *(g_u32x4a4_t*)(fp + i);   // dst[6] src[6] | port
+    const u32x4a4_t f = *(gu32x4a4_t*)(fp + i);   // dst[6] src[6] | port
     // the frame holds an Ethernet header inside the arena (the sum cannot wrap: off <= arena_len first)
     const bool inside = len >= 14u && off <= arena_len && (uint64_t)len <= arena_len - off;
     const bool go = inside && vd == VPCSUM_FLOW_HIT && (st & (VPCSUM_S_DONE | VPCSUM_S_BAD_DESC)) == VPCSUM_S_DONE && f.w != 0u;
     port_out[i] = go ? f.w : 0u;
     if (!go) return;
-    uint8_t* p = arena + off;
-    switch ((uint32_t)(uintptr_t)p & 3u) {
-    case 0: store_macs<0>(p, f.x, f.y, f.z); break;
-    case 1: store_macs<1>(p, f.x, f.y, f.z); break;
-    case 2: store_macs<2>(p, f.x, f.y, f.z); break;
-    default: store_macs<3>(p, f.x, f.y, f.z); break;
-    }
+    store_piece_any<12>(arena + off, Piece{f.x, f.y, f.z, 0u, 0u});
 }
 
 hipError_t launch_flow_lookup(const void* slots, uint32_t mask, uint32_t max_probe, uint8_t* touched,

@@ -44,27 +44,6 @@ constexpr int kSmallUnroll = 2;
 constexpr int kDefaultRot = -9;
 constexpr int kEsUnits = 8;   // K2 (DS): units whose out / status words a wave stages in LDS
 
-// Sum over the TEAM lanes of a team (aligned lane groups; every lane gets the total).  Teams of
-// up to 16 lanes reduce with DPP lane swizzles inside a row (xor 1, xor 2 by quad_perm, then
-// the half-row and row mirrors), one VALU op per step instead of an LDS-crossbar bpermute.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-template <int TEAM>
-__device__ __forceinline__ uint32_t team_sum(uint32_t v) {
-    if (TEAM <= 16) {
-        if (TEAM >= 2) v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-        if (TEAM >= 4) v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
-        if (TEAM >= 8) v = dpp_add<0x141>(v);   // row_half_mirror
-        if (TEAM >= 16) v = dpp_add<0x140>(v);  // row_mirror
-        return v;
-    }
-#pragma unroll
-    for (int m = TEAM / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, TEAM);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------
 // k_csum: team-per-packet compute / verify kernel, the fallback for arenas the buffer path
 // (K2, below) cannot address (> 4 GiB or not 16-B aligned), and the variant ids 2..11 of
