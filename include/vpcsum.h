@@ -49,8 +49,9 @@ extern "C" {
  * VPCSUM_NAT_TCP_REWRITES; a library from before answers that bit with "bad nat_mode", which is
  * how a caller probes for it; the flow table and its Fastpath; the TCP segment build
  * (vpcsum_tcp_build_async, vpcsum_ctx_build_tcp_frames, VPCsum.buildTcpFrames) and the TCP receive
- * (vpcsum_tcp_recv_async, vpcsum_tcp_digest_async, vpcsum_ctx_recv_tcp_frames, VPCsum.recvTcpFrames):
- * new symbols, which a caller probes for by looking them up. */
+ * (vpcsum_tcp_recv_async, vpcsum_tcp_digest_async, vpcsum_ctx_recv_tcp_frames, VPCsum.recvTcpFrames);
+ * the TCP send bursts (vpcsum_tcp_build_bursts_async, vpcsum_ctx_build_tcp_bursts,
+ * VPCsum.buildTcpBursts): new symbols, which a caller probes for by looking them up. */
 #define VPCSUM_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -493,6 +494,53 @@ int vpcsum_tcp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_sr
                            const vpcsum_tcphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* d_seg, uint32_t n,
                            uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream);
 
+/* TCP send bursts (additive, the ABI version stays 4): the segment build with the stack's slicing
+ * done on the device.  One record per SendingQueue.fetch() (TcpEntry.java:213-241) instead of one
+ * per frame: transmitTcpPsh (TcpStack.java:469-503) sends every piece of a fetch with the same
+ * template and the same flags, so a burst says where the run of payload starts, how long it is, its
+ * first sequence number and the MSS, and the frames are cut from it on the GPU. */
+typedef struct vpcsum_tcpburst {   /* one per fetch(); 32 bytes, 8-byte aligned */
+    uint64_t data_off;  /*  0  first payload byte in the source arena, any alignment          */
+    uint32_t data_len;  /*  8  payload bytes of the whole burst: min(window, queued) of fetch() */
+    uint32_t seq;       /* 12  sequence number of the first byte, host order                   */
+    uint32_t hdr;       /* 16  index into the template array                                   */
+    uint32_t first;     /* 20  index of the burst's first frame in the frame table             */
+    uint16_t mss;       /* 24  payload bytes of every frame but the last                       */
+    uint8_t  flags;     /* 26  TCP flags of every frame (the stack: PSH | ACK)                 */
+    uint8_t  rsv;       /* 27  must be 0                                                       */
+    uint32_t count;     /* 28  frames of the burst                                             */
+} vpcsum_tcpburst_t;
+
+/* Frame j of the table d_frame_off[0..n_frames) belongs to the last burst b with first[b] <= j (the
+ * search takes `first` to be non-decreasing).  With k = j - first[b], frame j is exactly the frame
+ * vpcsum_tcp_build_async builds from the record
+ *   {d_frame_off[j], data_off + k * mss, seq + k * mss (mod 2^32), hdr, frame_cap,
+ *    min(mss, data_len - k * mss), flags, 0},
+ * with the same d_frame_len[j] (required), d_out[j] and d_status[j] (each may be NULL).  A burst with
+ * data_len 0 has one frame without payload -- the ACK / FIN / RST of the per-segment build; its mss
+ * is not read -- so one call carries a whole transmit round.  frame_cap is one value for the call
+ * (umem chunks have one size).
+ * A whole burst is refused -- every frame of it gets d_frame_len 0, d_out 0, S_BAD_DESC, not one byte
+ * is written, nothing is read but the burst record and its template -- when hdr >= n_hdr or the
+ * template is one vpcsum_tcp_build_async refuses; flags & ~0x3f or rsv != 0; data_len > 0 and mss == 0;
+ * count != max(1, ceil(data_len / mss)); 40 (IPv4) or 20 (IPv6) + min(mss, data_len), the length field
+ * of the longest frame, > 65535; the header length + min(mss, data_len) > frame_cap; data_off >
+ * src_len or data_len > src_len - data_off (no wrapping).  A single frame is refused, its siblings
+ * built, only by its own destination: d_frame_off[j] + L > dst_len (no wrapping).  A frame no burst
+ * covers -- j - first[b] >= count[b], or no burst at or before it -- is refused; so is every frame
+ * when n_bursts is 0.
+ * Memory safety does not rest on the table being sorted: a frame is only built from a burst record
+ * it has checked itself against (first <= j, j - first < count) with all the bounds above, so an
+ * unsorted table gives refused or oddly attributed frames, never an access outside
+ * [d_frame_off[j], d_frame_off[j] + L) and the burst's own source range.
+ * Templates and frame lengths 4-byte aligned, burst records and frame offsets 8-byte aligned;
+ * n_frames and n_bursts each at most 2^28; n_frames == 0 returns 0.  Frames of one batch must not
+ * overlap each other or any payload range: the caller's rule, as for the build. */
+int vpcsum_tcp_build_bursts_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_src, uint64_t src_len,
+                                  const vpcsum_tcphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_tcpburst_t* d_burst,
+                                  uint32_t n_bursts, const uint64_t* d_frame_off, uint32_t n_frames, uint32_t frame_cap,
+                                  uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream);
+
 /* TCP receive (additive, the ABI version stays 4): the build's mirror.  What the userspace TCP stack
  * does on the host for every data segment it receives -- TcpStack.handleTcpEstablished ->
  * receivingQueue.store(new Segment(seq, tcpPkt.getData())), TcpStack.java:302-306; ReceivingQueue.store
@@ -722,6 +770,19 @@ int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* ctx, vpcsum_flowtab_t* tab,
 int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* ctx, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
                                 const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* h_seg, uint32_t n,
                                 uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket);
+/* vpcsum_tcp_build_bursts_async from host memory, in one submission: vpcsum_ctx_build_tcp_frames'
+ * rules with bursts for records.  h_dst must be inside a REGISTERED arena; a registered h_src is read
+ * in place; any other is staged: the span [min data_off, max data_off + data_len) over the bursts
+ * with a payload inside src_len goes to the device in one copy (refused if larger than the context's
+ * max_arena_bytes), data_off rebased in the library's own copy of the bursts -- the caller's arrays
+ * are not written.  n_frames, n_bursts and n_hdr are each at most the context's max_pkts.  At
+ * vpcsum_ctx_wait h_frame_len[j] (required), h_out[j] and h_status[j] (each may be NULL) hold what
+ * vpcsum_tcp_build_bursts_async writes.  Always launched: no service-grid, device-group or
+ * process-wide form. */
+int vpcsum_ctx_build_tcp_bursts(vpcsum_ctx_t* ctx, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
+                                const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpburst_t* h_burst,
+                                uint32_t n_bursts, const uint64_t* h_frame_off, uint32_t n_frames, uint32_t frame_cap,
+                                uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket);
 /* vpcsum_tcp_recv_async from host memory, in one submission: the payloads are written where they lie
  * in h_dst, through its mapping, so h_dst must be inside a REGISTERED arena (the connections'
  * receive buffers; an unregistered destination is refused, as in vpcsum_ctx_build_tcp_frames).  A
@@ -907,6 +968,14 @@ int Java_io_vproxy_vpcsum_VPCsum_natFlowForwardFrames(PNIEnv_vpcsum_long* env, i
 int Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
                                                 int64_t srcLen, void* hdr, int32_t nHdr, void* seg, int32_t n,
                                                 void* frameLen, void* out, void* status);
+/* VPCsum.buildTcpBursts(long ctx, MemorySegment dst, long dstLen, MemorySegment src, long srcLen,
+ *                       MemorySegment hdr, int nHdr, MemorySegment burst, int nBursts, MemorySegment frameOff,
+ *                       int nFrames, int frameCap, MemorySegment frameLen, MemorySegment out,
+ *                       MemorySegment status) -> long ticket (vpcsum_ctx_build_tcp_bursts) */
+int Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
+                                                int64_t srcLen, void* hdr, int32_t nHdr, void* burst, int32_t nBursts,
+                                                void* frameOff, int32_t nFrames, int32_t frameCap, void* frameLen,
+                                                void* out, void* status);
 /* VPCsum.recvTcpFrames(long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment rx, int n,
  *                      MemorySegment dst, long dstLen, MemorySegment stored, MemorySegment out,
  *                      MemorySegment status) -> long ticket (vpcsum_ctx_recv_tcp_frames) */

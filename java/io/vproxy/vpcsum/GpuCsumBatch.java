@@ -416,6 +416,25 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * {@link #buildTcp} with the slicing on the GPU: one record per sendingQueue.fetch()
+     * ({@link VPCsum#tcpBurst}: dataOff / seq at ackSeq, dataLen = min(window, queued), the queue's
+     * mss, flags PSH|ACK; dataLen 0 for a FIN / ACK / RST) instead of one per Segment.
+     * {@code frameOff} lists the {@code nFrames} TX chunks of the round (u64 offsets into the umem,
+     * each with {@code frameCap} bytes of room); burst b takes frameOff[first .. first + count).
+     * Fills {@code frameLenOut} (u32 per frame): the frame's length for the TX descriptor, or 0 -- the
+     * frame was refused, build that segment on the host.  Needs a library with the entry
+     * ({@code VPCsumLib.hasTcpBursts()}); SYNs stay on the host.
+     */
+    public MemorySegment buildTcpBursts(MemorySegment sendBuf, long sendBufLen, MemorySegment hdr, int nHdr, MemorySegment burst,
+                                        int nBursts, MemorySegment frameOff, int nFrames, int frameCap,
+                                        MemorySegment frameLenOut, MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().buildTcpBursts(env, ctx, umem, umemLen, sendBuf, sendBufLen, hdr, nHdr, burst, nBursts, frameOff,
+            nFrames, frameCap, frameLenOut, MemorySegment.NULL, statusOut);
+        VPCsum.get().waitFor(env, ctx, t);
+        return frameLenOut;
+    }
+
+    /**
      * The data segments the userspace TCP stack receives (TcpStack.handleTcpEstablished ->
      * receivingQueue.store): {@code count} frames of the umem described in {@code frameDesc} (the
      * parse's descriptors), one record each in {@code rx} ({@link VPCsum#tcpRx}: for a PSH segment

@@ -179,6 +179,33 @@ public class VPCsum {
         seg.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 31, (byte) 0);
     }
 
+    /** bytes of one vpcsum_tcpburst_t record ({@link #tcpBurst}) */
+    public static final int TCP_BURST = 32;
+
+    /** Fill the 32-byte burst record at {@code burst[off..]}: one SendingQueue.fetch().  {@code dataOff}
+     * is where the byte with sequence number ackSeq lies in the source arena, {@code dataLen} =
+     * min(window, queued bytes from ackSeq on), {@code seq} = ackSeq (the first Segment's
+     * seqBeginInclusive), {@code hdrIndex} the template, {@code firstFrame} the index of the burst's
+     * first frame in the call's frame table (non-decreasing over the records), {@code mss} the
+     * sendingQueue's, {@code flags} the TCP flags of every frame (PSH | ACK).  The frame count,
+     * max(1, ceil(dataLen / mss)), is written here and returned: the caller reserves that many chunks.
+     * dataLen 0: one frame without payload (FIN / ACK / RST), mss ignored. */
+    public static int tcpBurst(MemorySegment burst, long off, long dataOff, int dataLen, int seq, int hdrIndex, int firstFrame,
+                               int mss, int flags) {
+        final var LE = java.nio.ByteOrder.LITTLE_ENDIAN;
+        int count = dataLen == 0 ? 1 : (int) ((Integer.toUnsignedLong(dataLen) - 1) / mss + 1);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off, dataOff);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 8, dataLen);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 12, seq);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 16, hdrIndex);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 20, firstFrame);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_SHORT_UNALIGNED.withOrder(LE), off + 24, (short) mss);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 26, (byte) (flags & 0x3f));
+        burst.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 27, (byte) 0);
+        burst.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 28, count);
+        return count;
+    }
+
     /** bytes of one vpcsum_tcprx_t receive record ({@link #tcpRx}) */
     public static final int TCP_RX = 16;
     /** bytes of one vpcsum_tcpinfo_t segment digest ({@link #tcpInfoSeq} and its neighbours) */
@@ -661,6 +688,49 @@ public class VPCsum {
         try {
             ERR = (int) buildTcpFramesMH.invokeExact(ENV.MEMORY, ctx, dst, dstLen, src, srcLen, hdr, nHdr, seg, n, frameLen, out,
                 status);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    /* Resolved on first use, not in the static initialiser: the entry came after ABI version 4 was
+     * fixed, and a library from before it must still initialise this class (VPCsumLib.hasTcpBursts). */
+    private static volatile MethodHandle buildTcpBurstsMH;
+
+    /** The TCP send bursts (vpcsum_ctx_build_tcp_bursts): {@link #buildTcpFrames} with one record of
+     * {@link #TCP_BURST} bytes ({@link #tcpBurst}) per SendingQueue.fetch() instead of one per frame.
+     * {@code frameOff} holds {@code nFrames} u64 frame offsets of {@code dst}, every frame with
+     * {@code frameCap} bytes of room (the umem chunk's); the frames of burst b are
+     * frameOff[first .. first + count), cut from the burst's payload run on the GPU.  After
+     * {@link #waitFor}: frameLen[j] (u32) the frame's length, 0 for a refused frame (status[j]
+     * S_BAD_DESC, nothing written); out / status may be MemorySegment.NULL. */
+    public long buildTcpBursts(PNIEnv ENV, long ctx, MemorySegment dst, long dstLen, MemorySegment src, long srcLen,
+                               MemorySegment hdr, int nHdr, MemorySegment burst, int nBursts, MemorySegment frameOff, int nFrames,
+                               int frameCap, MemorySegment frameLen, MemorySegment out, MemorySegment status)
+        throws java.io.IOException {
+        MethodHandle MH = buildTcpBurstsMH;
+        if (MH == null) {
+            if (!VPCsumLib.hasTcpBursts()) {
+                throw new java.io.IOException("libvpcsum has no buildTcpBursts: the library is older than this binding");
+            }
+            MH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+                "Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts", long.class /* ctx */, MemorySegment.class /* dst */,
+                long.class /* dstLen */, MemorySegment.class /* src */, long.class /* srcLen */, MemorySegment.class /* hdr */,
+                int.class /* nHdr */, MemorySegment.class /* burst */, int.class /* nBursts */, MemorySegment.class /* frameOff */,
+                int.class /* nFrames */, int.class /* frameCap */, MemorySegment.class /* frameLen */,
+                MemorySegment.class /* out */, MemorySegment.class /* status */);
+            buildTcpBurstsMH = MH;
+        }
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) MH.invokeExact(ENV.MEMORY, ctx, dst, dstLen, src, srcLen, hdr, nHdr, burst, nBursts, frameOff, nFrames,
+                frameCap, frameLen, out, status);
         } catch (Throwable THROWABLE) {
             throw PanamaUtils.convertInvokeExactException(THROWABLE);
         }

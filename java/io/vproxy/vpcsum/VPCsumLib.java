@@ -45,6 +45,17 @@ final class VPCsumLib {
         }
     }
 
+    /** Whether the loaded library exports {@code symbol}: how a caller probes for an entry point added
+     * since ABI version 4 was fixed (include/vpcsum.h), e.g. before it plans a transmit round as bursts. */
+    static boolean has(String symbol) {
+        return SymbolLookup.loaderLookup().find(symbol).isPresent();
+    }
+
+    /** The TCP send bursts ({@link VPCsum#buildTcpBursts}, {@link GpuCsumBatch#buildTcpBursts}). */
+    static boolean hasTcpBursts() {
+        return has("Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts");
+    }
+
     /** IOException unless the loaded library speaks ABI {@code expected} (VPCsum.ABI_VERSION). */
     static void requireAbi(int expected) throws IOException {
         int v = abiVersion();

@@ -9,9 +9,13 @@ over --launches launches after a warm-up, legs in alternating rounds:
   c  that 2-D copy alone: the copy ceiling
   d  for scale, a contiguous device copy of the same payload bytes (no frames): what moving
      2 x data_len bytes per segment costs when nothing is strided
+  s  vpcsum_tcp_build_bursts_async (k_tcp_build_bursts): the same frames described as bursts of 45, 10
+     and 1 frames (s45, s10, s1) and a frame table, the cut made on the device; its yardstick is leg a of
+     the same process
 Algorithmic bytes per segment: data_len read + L written + the 32-byte record.  Before timing, b's
-frames are compared with a's: the two must build the same bytes.
-Prints one JSON line.  usage: segbench.py [segments] [--launches N]"""
+and s's frames are compared with a's: all must build the same bytes.
+Prints one JSON line.  usage: segbench.py [segments] [--launches N] [--lib libvpcsum.so]
+(--lib: another build of the library, e.g. one compiled with -DVPCSUM_BURST_BINARY_SEARCH)"""
 import ctypes
 import json
 import os
@@ -26,6 +30,8 @@ from vproxy_amd import vpcsum as V  # noqa: E402
 n = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 1 << 17
 launches = int(sys.argv[sys.argv.index("--launches") + 1]) if "--launches" in sys.argv else 50
 rounds = 3
+if "--lib" in sys.argv:
+    V.LIB = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 STRIDE, HEADROOM, HLEN = 2048, 384, 54
 
 V.lib()
@@ -117,6 +123,30 @@ for data_len in (1360, 1460):
         flat.copy_(src)
 
     legs = {"a_tcp_build": leg_a, "b_copy2d_plus_compute_write": leg_b, "c_copy2d_alone": leg_c, "d_contiguous_copy": leg_d}
+    # s: the same frames as bursts of 45, 10 and 1 frames over one frame table
+    dst3 = torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda")
+    flen3, out3, st3 = torch.zeros_like(flen), torch.zeros_like(out), torch.zeros_like(st)
+    record_bytes = {"a": n * 32}
+    for per in (45, 10, 1):
+        nb = (n + per - 1) // per
+        bu = np.zeros(nb, V.TCPBURST_DTYPE)
+        first = np.arange(nb, dtype=np.uint64) * per
+        bu["first"], bu["data_off"] = first, first * data_len
+        bu["count"] = np.minimum(per, n - first)
+        bu["data_len"] = bu["count"] * data_len
+        bu["seq"] = (first * data_len & 0xffffffff).astype(np.uint32)
+        bu["mss"], bu["flags"] = data_len, 0x18
+        d_bu = dev(bu)
+
+        def leg_s(d_bu=d_bu, nb=nb):
+            V.tcp_build_bursts(dst3, src, d_hdr, 1, d_bu, nb, foff, n, STRIDE - HEADROOM, flen3, out3, st3)
+
+        dst3.zero_()
+        leg_s()
+        torch.cuda.synchronize()
+        assert torch.equal(dst3, built) and torch.equal(out3, out) and torch.equal(flen3, flen) and torch.equal(st3, st), per
+        legs[f"s{per}_tcp_build_bursts"] = leg_s
+        record_bytes[f"s{per}"] = nb * 32 + n * 8
     us = {k: [] for k in legs}
     for _ in range(rounds):
         for k, fn in legs.items():
@@ -127,9 +157,14 @@ for data_len in (1360, 1460):
     for k, v in us.items():
         med = sorted(v)[len(v) // 2]
         r[k] = {"us_rounds": v, "us_median": med, "Mseg_per_s": round(n / med, 2), "GB_per_s": round(n * bytes_per_seg / med / 1e3, 1)}
+    a_spread = max(us["a_tcp_build"]) / min(us["a_tcp_build"]) - 1
+    r["a_round_spread"] = round(a_spread, 4)
+    for per in (45, 10, 1):
+        r[f"s{per}_over_a"] = round(r[f"s{per}_tcp_build_bursts"]["us_median"] / r["a_tcp_build"]["us_median"], 4)
+    r["record_bytes_uploaded"] = record_bytes
     r["b_over_a"] = round(r["b_copy2d_plus_compute_write"]["us_median"] / r["a_tcp_build"]["us_median"], 3)
     r["a_over_c"] = round(r["a_tcp_build"]["us_median"] / r["c_copy2d_alone"]["us_median"], 3)
     res[f"data_len_{data_len}"] = r
     r["d_contiguous_copy"]["GB_per_s"] = round(n * 2 * data_len / r["d_contiguous_copy"]["us_median"] / 1e3, 1)   # its own bytes
-    del src, dst, dst2, built, flat
+    del src, dst, dst2, dst3, built, flat
 print(json.dumps(res))

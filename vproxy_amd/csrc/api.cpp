@@ -26,6 +26,7 @@
 #include "flow_table.h"
 #include "internal.h"
 #include "tcp_build.h"
+#include "tcp_burst.h"
 #include "tcp_recv.h"
 #include "vpcsum.h"
 
@@ -204,6 +205,7 @@ struct Slot {
     Mapped<vpcsum_tcphdr_t> h_thdr;
     Mapped<uint32_t> h_tlen;           // (a TCP receive batch's stored counts too)
     Mapped<vpcsum_tcprx_t> h_trx;      // a TCP receive batch's records
+    Mapped<vpcsum_tcpburst_t> h_tburst;   // a TCP burst batch's records (its frame table: h_foff)
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool busy = false;                 // `batch` is in flight
@@ -1793,6 +1795,32 @@ int vpcsum_tcp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_sr
     } VPC_CATCH("vpcsum_tcp_build_async")
 }
 
+int vpcsum_tcp_build_bursts_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_src, uint64_t src_len,
+                                  const vpcsum_tcphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_tcpburst_t* d_burst,
+                                  uint32_t n_bursts, const uint64_t* d_frame_off, uint32_t n_frames, uint32_t frame_cap,
+                                  uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream) {
+    try {
+        if (n_frames == 0) return 0;
+        if (!d_dst) return fail("vpcsum_tcp_build_bursts_async: NULL destination arena");
+        if (!d_src && src_len) return fail("vpcsum_tcp_build_bursts_async: NULL source arena");
+        if (!d_hdr && n_hdr) return fail("vpcsum_tcp_build_bursts_async: NULL templates");
+        if (!d_burst && n_bursts) return fail("vpcsum_tcp_build_bursts_async: NULL bursts");
+        if (!d_frame_off) return fail("vpcsum_tcp_build_bursts_async: NULL frame offsets");
+        if (!d_frame_len) return fail("vpcsum_tcp_build_bursts_async: NULL frame lengths");
+        if ((uintptr_t)d_burst & 7) return fail("vpcsum_tcp_build_bursts_async: bursts not 8-byte aligned");
+        if ((uintptr_t)d_frame_off & 7) return fail("vpcsum_tcp_build_bursts_async: frame offsets not 8-byte aligned");
+        if ((uintptr_t)d_hdr & 3) return fail("vpcsum_tcp_build_bursts_async: templates not 4-byte aligned");
+        if ((uintptr_t)d_frame_len & 3) return fail("vpcsum_tcp_build_bursts_async: frame lengths not 4-byte aligned");
+        if ((uintptr_t)d_out & 3) return fail("vpcsum_tcp_build_bursts_async: out words not 4-byte aligned");
+        if (n_frames > (1u << 28)) return fail("vpcsum_tcp_build_bursts_async: %u frames > 2^28", n_frames);
+        if (n_bursts > (1u << 28)) return fail("vpcsum_tcp_build_bursts_async: %u bursts > 2^28", n_bursts);
+        VPC_CHECK(launch_tcp_build_bursts(d_dst, dst_len, d_src, src_len, d_hdr, n_hdr, d_burst, n_bursts, d_frame_off, n_frames,
+                                          frame_cap, d_frame_len, d_out, d_status, (hipStream_t)stream),
+                  "TCP burst build launch");
+        return 0;
+    } VPC_CATCH("vpcsum_tcp_build_bursts_async")
+}
+
 int vpcsum_tcp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, const vpcsum_tcprx_t* d_rx,
                           uint32_t n, uint8_t* d_dst, uint64_t dst_len, uint32_t* d_stored, uint32_t* d_out, uint8_t* d_status,
                           void* stream) {
@@ -1954,6 +1982,60 @@ int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_le
         }
         return slot_commit(s, b, ticket);
     } VPC_CATCH("vpcsum_ctx_build_tcp_frames")
+}
+
+// The TCP send bursts of host memory: vpcsum_ctx_build_tcp_frames with bursts for records and the
+// frame table beside them.  Always launched, on the slot's one stream.
+int vpcsum_ctx_build_tcp_bursts(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
+                                const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpburst_t* h_burst,
+                                uint32_t n_bursts, const uint64_t* h_frame_off, uint32_t n_frames, uint32_t frame_cap,
+                                uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
+    const char* what = "vpcsum_ctx_build_tcp_bursts";
+    try {
+        if (!c || !ticket) return fail("%s: NULL context or ticket", what);
+        const uint32_t n = n_frames;
+        if (n > c->max_pkts) return fail("%s: %u frames > capacity %u", what, n, c->max_pkts);
+        if (n_bursts > c->max_pkts) return fail("%s: %u bursts > capacity %u", what, n_bursts, c->max_pkts);
+        if (n_hdr > c->max_pkts) return fail("%s: %u templates > capacity %u", what, n_hdr, c->max_pkts);
+        if (n && (!h_dst || !h_frame_off || !h_frame_len || (!h_burst && n_bursts) || (!h_hdr && n_hdr) || (!h_src && src_len)))
+            return fail("%s: NULL destination, source, templates, bursts, frame offsets or frame lengths", what);
+        std::lock_guard<std::mutex> lk(c->mu);
+        VPC_ON_DEVICE(c->device);
+        uint8_t* base = n ? mapped_dev(c, h_dst, dst_len) : nullptr;
+        if (n && !base) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
+        // the source: read in place when registered, else the span of the payloads that lie inside it
+        const uint8_t* src_dev = n && src_len ? mapped_dev(c, h_src, src_len) : nullptr;
+        const bool staged = n && src_len && !src_dev;
+        TcpPayloadSpan sp = {0, 0};
+        if (staged && !tcp_burst_payload_span(h_burst, n_bursts, src_len, c->max_arena, &sp))
+            return fail("%s: the payloads span %llu bytes > capacity %llu", what, (unsigned long long)sp.len,
+                        (unsigned long long)c->max_arena);
+        Batch b;
+        Slot* slot = slot_acquire(c, &b.ticket);
+        if (!slot) return -1;
+        Slot& s = *slot;
+        b.n = n;
+        b.zero_copy = true;   // the frames are written in place through the destination's mapping
+        if (n) {
+            // bursts, templates and frame lengths: pinned; the frame table in the slot's own
+            if (slot_scratch(c, what, s.h_tburst, s.h_thdr, s.h_tlen) != 0) return -1;
+            b.hand_back({status_of(c, s, false, h_status, n), {h_frame_len, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
+            memcpy(s.h_foff.p, h_frame_off, (size_t)n * 8);
+            if (n_bursts) memcpy(s.h_tburst.p, h_burst, (size_t)n_bursts * sizeof(vpcsum_tcpburst_t));
+            if (n_hdr) memcpy(s.h_thdr.p, h_hdr, (size_t)n_hdr * sizeof(vpcsum_tcphdr_t));
+            if (staged) {
+                // the library's copy of the bursts names the staged span
+                tcp_burst_rebase_payloads(s.h_tburst.p, n_bursts, src_len, sp.lo);
+                if (sp.len) memcpy(s.h_arena.p, h_src + sp.lo, sp.len);   // pageable -> pinned staging
+                if (stage_frames_up(s, sp.len) != 0) return -1;
+            }
+            VPC_CHECK(launch_tcp_build_bursts(base, dst_len, staged ? s.d_arena.p : src_dev, staged ? sp.len : src_len,
+                                              s.h_thdr.dev, n_hdr, s.h_tburst.dev, n_bursts, s.h_foff.dev, n, frame_cap,
+                                              s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
+                      "TCP burst build launch");
+        }
+        return slot_commit(s, b, ticket);
+    } VPC_CATCH("vpcsum_ctx_build_tcp_bursts")
 }
 
 // The TCP receive of host memory: payloads written in place into a registered destination, the
@@ -2657,6 +2739,21 @@ int Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames(PNIEnv_vpcsum_long* env, int64_t
         return vpcsum_ctx_build_tcp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)dst, (uint64_t)dstLen, (const uint8_t*)src,
                                            (uint64_t)srcLen, (const vpcsum_tcphdr_t*)hdr, (uint32_t)nHdr,
                                            (const vpcsum_tcpseg_t*)seg, (uint32_t)n, (uint32_t*)frameLen, (uint32_t*)out,
+                                           (uint8_t*)status, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
+                                                int64_t srcLen, void* hdr, int32_t nHdr, void* burst, int32_t nBursts,
+                                                void* frameOff, int32_t nFrames, int32_t frameCap, void* frameLen,
+                                                void* out, void* status) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts",
+                         nFrames < 0 || nBursts < 0 || nHdr < 0 || frameCap < 0 || dstLen < 0 || srcLen < 0,
+                         "buildTcpBursts: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_build_tcp_bursts((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)dst, (uint64_t)dstLen, (const uint8_t*)src,
+                                           (uint64_t)srcLen, (const vpcsum_tcphdr_t*)hdr, (uint32_t)nHdr,
+                                           (const vpcsum_tcpburst_t*)burst, (uint32_t)nBursts, (const uint64_t*)frameOff,
+                                           (uint32_t)nFrames, (uint32_t)frameCap, (uint32_t*)frameLen, (uint32_t*)out,
                                            (uint8_t*)status, t);
     });
 }

@@ -115,6 +115,13 @@ hipError_t launch_tcp_build(uint8_t* dst, uint64_t dst_len, const uint8_t* src, 
                             const vpcsum_tcphdr_t* hdrs, uint32_t n_hdr, const vpcsum_tcpseg_t* segs, uint32_t n,
                             uint32_t* frame_len_out, uint32_t* out, uint8_t* status, hipStream_t stream);
 
+// TCP send bursts (tcp_burst.hip k_tcp_build_bursts, vpcsum.h vpcsum_tcp_build_bursts_async's rule):
+// frame j of the table from the burst it belongs to, cut and built on the device
+hipError_t launch_tcp_build_bursts(uint8_t* dst, uint64_t dst_len, const uint8_t* src, uint64_t src_len,
+                                   const vpcsum_tcphdr_t* hdrs, uint32_t n_hdr, const vpcsum_tcpburst_t* bursts,
+                                   uint32_t n_bursts, const uint64_t* frame_off, uint32_t n_frames, uint32_t frame_cap,
+                                   uint32_t* frame_len_out, uint32_t* out, uint8_t* status, hipStream_t stream);
+
 // TCP receive (tcp_recv.hip, vpcsum.h vpcsum_tcp_recv_async's rule): descriptor i verified as
 // VPCSUM_MODE_VERIFY does and, under rx[i], its payload past `skip` stored at dst + rx[i].dst_off;
 // stored[i] = the byte count, 0 for a refused record; out / status may be NULL.  k_tcp_digest: info[i]

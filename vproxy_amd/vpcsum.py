@@ -60,6 +60,11 @@ TCPHDR_DTYPE = np.dtype([("eth_dst", "u1", 6), ("eth_src", "u1", 6), ("l2_len", 
 # order), template index, the room at frame_off, payload length, TCP flags
 TCPSEG_DTYPE = np.dtype([("frame_off", "<u8"), ("data_off", "<u8"), ("seq", "<u4"), ("hdr", "<u4"), ("frame_cap", "<u4"),
                          ("data_len", "<u2"), ("flags", "u1"), ("rsv", "u1")])
+# vpcsum_tcpburst_t (32 B): one SendingQueue.fetch() of the TCP send bursts -- the run of payload, the
+# first sequence number (host order), template index, the burst's first frame in the frame table, MSS,
+# TCP flags, frame count
+TCPBURST_DTYPE = np.dtype([("data_off", "<u8"), ("data_len", "<u4"), ("seq", "<u4"), ("hdr", "<u4"), ("first", "<u4"),
+                           ("mss", "<u2"), ("flags", "u1"), ("rsv", "u1"), ("count", "<u4")])
 # vpcsum_tcprx_t (16 B): what the TCP receive does with descriptor i -- where payload byte `skip`
 # goes in the receive arena, the room there, the bytes already received, TCPRX_STORE or 0 (verify only)
 TCPRX_DTYPE = np.dtype([("dst_off", "<u8"), ("dst_cap", "<u4"), ("skip", "<u2"), ("ops", "u1"), ("rsv", "u1")])
@@ -105,10 +110,12 @@ EXPORTS = [
     "vpcsum_tcp_build_async", "vpcsum_ctx_build_tcp_frames", "Java_io_vproxy_vpcsum_VPCsum_buildTcpFrames",
     "vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames",
     "Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames",
+    "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts", "Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts",
 ]
 
 # additive entry points this binding probes for instead of requiring (see _declare)
-_PROBED = ("vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames")
+_PROBED = ("vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames",
+           "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts")
 
 
 class VpcsumUnavailable(RuntimeError):
@@ -289,12 +296,14 @@ def _declare(L):
         "vpcsum_tcp_recv_async": ([P, U64, P, P, U32, P, U64, P, P, P, P], I),
         "vpcsum_tcp_digest_async": ([P, U64, P, U32, P, P], I),
         "vpcsum_ctx_recv_tcp_frames": ([P, P, U64, P, P, U32, P, U64, P, P, P, P], I),
+        "vpcsum_tcp_build_bursts_async": ([P, U64, P, U64, P, U32, P, U32, P, U32, U32, P, P, P, P], I),
+        "vpcsum_ctx_build_tcp_bursts": ([P, P, U64, P, U64, P, U32, P, U32, P, U32, U32, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
-        # The TCP receive came after ABI version 4 was fixed: a caller probes for it by looking the
-        # symbols up (include/vpcsum.h).  So does this binding -- it loads a library from before them
-        # (tools/ab_libs.sh compares against one), and using tcp_recv() on such a library raises
-        # ctypes' "undefined symbol", never a fallback.
+        # The TCP receive and the TCP send bursts came after ABI version 4 was fixed: a caller probes
+        # for them by looking the symbols up (include/vpcsum.h).  So does this binding -- it loads a
+        # library from before them (tools/ab_libs.sh compares against one), and using tcp_recv() or
+        # tcp_build_bursts() on such a library raises ctypes' "undefined symbol", never a fallback.
         if name in _PROBED and not hasattr(L, name):
             continue
         f = getattr(L, name)
@@ -557,6 +566,24 @@ def tcp_build(dst, src, hdrs, n_hdr: int, segs, n: int, frame_len, out=None, sta
     _check(lib().vpcsum_tcp_build_async(_ptr(dst), dst.numel() * dst.element_size(), _ptr(src),
                                         src.numel() * src.element_size(), _ptr(hdrs), n_hdr, _ptr(segs), n, _ptr(frame_len),
                                         _ptr(out), _ptr(status), _stream(stream)), "vpcsum_tcp_build_async")
+
+
+def tcp_build_bursts(dst, src, hdrs, n_hdr: int, bursts, n_bursts: int, frame_off, n_frames: int, frame_cap: int, frame_len,
+                     out=None, status=None, stream=None):
+    """vpcsum_tcp_build_bursts_async on device tensors: tcp_build() with one record per fetch().
+    `bursts` n_bursts x 32 bytes (TCPBURST_DTYPE, `first` non-decreasing), `frame_off` n_frames x uint64,
+    `frame_cap` the room at every frame; frame j is piece j - first of the last burst that starts at or
+    before it, cut on the device.  `frame_len` / `out` / `status` are per frame, as tcp_build() writes them."""
+    assert hdrs.numel() * hdrs.element_size() >= n_hdr * TCPHDR_DTYPE.itemsize
+    assert bursts.numel() * bursts.element_size() >= n_bursts * TCPBURST_DTYPE.itemsize
+    assert frame_off.numel() * frame_off.element_size() >= n_frames * 8
+    assert frame_len.numel() * frame_len.element_size() >= n_frames * 4
+    assert out is None or out.numel() * out.element_size() >= n_frames * 4
+    assert status is None or status.numel() >= n_frames
+    _check(lib().vpcsum_tcp_build_bursts_async(_ptr(dst), dst.numel() * dst.element_size(), _ptr(src),
+                                               src.numel() * src.element_size(), _ptr(hdrs), n_hdr, _ptr(bursts), n_bursts,
+                                               _ptr(frame_off), n_frames, frame_cap, _ptr(frame_len), _ptr(out), _ptr(status),
+                                               _stream(stream)), "vpcsum_tcp_build_bursts_async")
 
 
 def tcp_recv(arena, desc, rx, n: int, dst, stored, out=None, status=None, stream=None):
@@ -858,6 +885,30 @@ class Context:
                                                  None if out is None else out.ctypes.data,
                                                  None if status is None else status.ctypes.data, ctypes.byref(t)),
                "vpcsum_ctx_build_tcp_frames")
+        self.wait(t.value)
+        return frame_len, out, status
+
+    def build_tcp_bursts(self, dst: np.ndarray, src: np.ndarray, hdrs: np.ndarray, bursts: np.ndarray, frame_off: np.ndarray,
+                         frame_cap: int, want_out: bool = True, want_status: bool = True):
+        """vpcsum_ctx_build_tcp_bursts: build_tcp_frames with one record per fetch() -- the frames of
+        `frame_off` cut from `bursts` (TCPBURST_DTYPE) on the device, each with `frame_cap` bytes of
+        room.  `dst` must lie in a registered arena; a registered `src` is read in place, any other
+        staged.  Returns (frame_len, out, status) per frame; frame_len 0: the frame was refused."""
+        assert hdrs.dtype == TCPHDR_DTYPE and bursts.dtype == TCPBURST_DTYPE
+        n, n_bursts, n_hdr = len(frame_off), len(bursts), len(hdrs)
+        hd, bu = np.ascontiguousarray(hdrs), np.ascontiguousarray(bursts)
+        fo = np.ascontiguousarray(frame_off, dtype=np.uint64)
+        frame_len = np.zeros(n, np.uint32)
+        out = np.zeros(n, np.uint32) if want_out else None
+        status = np.zeros(n, np.uint8) if want_status else None
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_build_tcp_bursts(self.h, dst.ctypes.data, dst.nbytes, src.ctypes.data if src.nbytes else None,
+                                                 src.nbytes, hd.ctypes.data if n_hdr else None, n_hdr,
+                                                 bu.ctypes.data if n_bursts else None, n_bursts,
+                                                 fo.ctypes.data if n else None, n, frame_cap, frame_len.ctypes.data,
+                                                 None if out is None else out.ctypes.data,
+                                                 None if status is None else status.ctypes.data, ctypes.byref(t)),
+               "vpcsum_ctx_build_tcp_bursts")
         self.wait(t.value)
         return frame_len, out, status
 

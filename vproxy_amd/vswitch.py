@@ -555,6 +555,28 @@ def plan_tcp_store(expecting_seq: int, seq: int, data_len: int):
     return 0, data_len
 
 
+def plan_tcp_fetch(ack_seq: int, window: int, mss: int, queue_begin: int, queue_end: int, ack_splits_piece: bool = False):
+    """What SendingQueue.fetch() / fetch0() (TcpEntry.java:213-280) return for a sending queue whose
+    queued pieces cover [queue_begin, queue_end) without a gap, as one burst: ``(seq, data_len, count)``
+    -- the fields of a TCPBURST_DTYPE record (`seq` is the stack's long: the record takes its low 32
+    bits; the payload is the queue's bytes from ``seq`` on) -- or None when fetch() returns no segment.
+    Its quirks, kept: the cut starts at ackSeq, not at fetchSeq, so every call resends all that is
+    unacknowledged; the first piece is min(mss, window) and every later one mss or what is left of
+    the window, which is the cut of min(window, queued) bytes into pieces of mss; a queue that is
+    empty, begins past ackSeq or ends at or before it gives nothing; a window of 0 gives nothing --
+    except that fetch0(ackSeq, ackSeq) on a queued piece that begins BEFORE ackSeq and ends after it
+    returns a segment without data, which transmitTcpPsh sends as a bare PSH | ACK: a caller that
+    knows ackSeq splits a piece says so with `ack_splits_piece` and gets ``(seq, 0, 1)``, the burst
+    of one frame without payload.  How the queue was pushed in pieces changes nothing else."""
+    assert mss > 0 and window >= 0
+    if queue_end <= queue_begin or queue_begin > ack_seq or ack_seq >= queue_end:
+        return None
+    data_len = min(window, queue_end - ack_seq)
+    if data_len == 0:
+        return (ack_seq, 0, 1) if ack_splits_piece else None
+    return ack_seq, data_len, (data_len + mss - 1) // mss
+
+
 def verify_frames(ctx: "V.Context", arena: np.ndarray, desc: np.ndarray):
     """Ingress verify: (out, status) with S_IP_OK / S_L4_OK / S_UDP_NOCSUM per frame."""
     return ctx.run(arena, desc, V.MODE_VERIFY)
