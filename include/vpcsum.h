@@ -51,7 +51,10 @@ extern "C" {
  * (vpcsum_tcp_build_async, vpcsum_ctx_build_tcp_frames, VPCsum.buildTcpFrames) and the TCP receive
  * (vpcsum_tcp_recv_async, vpcsum_tcp_digest_async, vpcsum_ctx_recv_tcp_frames, VPCsum.recvTcpFrames);
  * the TCP send bursts (vpcsum_tcp_build_bursts_async, vpcsum_ctx_build_tcp_bursts,
- * VPCsum.buildTcpBursts): new symbols, which a caller probes for by looking them up. */
+ * VPCsum.buildTcpBursts); the UDP datagram build and receive (vpcsum_udp_build_async,
+ * vpcsum_udp_recv_async, vpcsum_ctx_build_udp_frames, vpcsum_ctx_recv_udp_frames,
+ * VPCsum.buildUdpFrames, VPCsum.recvUdpFrames): new symbols, which a caller probes for by looking
+ * them up. */
 #define VPCSUM_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -600,6 +603,95 @@ int vpcsum_tcp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcs
 int vpcsum_tcp_digest_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc,
                             uint32_t n, vpcsum_tcpinfo_t* d_info, void* stream);
 
+/* UDP datagram build (additive, the ABI version stays 4): the TCP segment build for the stack's UDP
+ * sockets (UdpListenEntry: the vswitch's DNS, the datagram FDs).  What UdpOutput.sendUdp does on the
+ * host for every datagram of sendingQueue.fetch() (UdpOutput.java:47-70: UdpUtils.buildCommonUdpResponse
+ * / buildIpResponse, UdpUtils.java:15-56; on the EnhancedUDPEntry's Fastpath a new Ethernet header,
+ * L4Output.java:39-55; XDPIface.sendPacket's copy into a umem chunk), as one fused copy-and-checksum:
+ * the payload is read once and written once, the UDP sum accumulated on the way, the headers
+ * generated from the template; the result equals getRawPacket(0) of what sendUdp builds, behind the
+ * Fastpath's Ethernet header.
+ *
+ * The template is vpcsum_tcphdr_t's 64 bytes, one per EnhancedUDPEntry (remote, local): src / sport
+ * from udp.listening, dst / dport from the datagram's remote, eth_dst / eth_src / l2_len 14 from the
+ * entry's Fastpath (l2_len 0: the frame starts at the IP header), tos / ttl / ident / frag as for TCP
+ * (the stack: 0, 64, 0, 0).  Bytes 52..57 (ack, window) and rsv must be 0. */
+typedef vpcsum_tcphdr_t vpcsum_udphdr_t;
+
+typedef struct vpcsum_udpdg {      /* one per datagram to build; 32 bytes, 8-byte aligned */
+    uint64_t frame_off;    /*  0  where the frame starts in the destination arena, any alignment */
+    uint64_t data_off;     /*  8  where the payload starts in the source arena, any alignment */
+    uint32_t hdr;          /* 16  index into the template array */
+    uint32_t frame_cap;    /* 20  room at frame_off (the chunk's); a frame that needs more is refused */
+    uint32_t data_len;     /* 24  payload bytes; 0 is a legal datagram.  32 bits: a length the 16-bit
+                                  fields cannot hold is refused, not truncated */
+    uint32_t rsv;          /* 28  must be 0 */
+} vpcsum_udpdg_t;
+
+/* Frame i, of length L = l2_len + (20 | 40) + 8 + data_len, at d_dst + frame_off:
+ *   Ethernet (l2_len 14): eth_dst, eth_src, EtherType, as in the TCP build.
+ *   IPv4 (Ipv4Packet.genHeaderWithChecksumUnfilled :279-294, IHL 5): 45, tos, totalLength 28 +
+ *     data_len, ident, frag, ttl, 11, the header sum (Utils.calculateChecksum over the 20 bytes),
+ *     src[0..3], dst[0..3].
+ *   IPv6 (Ipv6Packet.buildPacket :185-190, no extension headers, flow label 0): 60 | tos>>4,
+ *     (tos<<4) & 0xff, 00 00, payloadLength 8 + data_len, 11, ttl, src, dst.
+ *   UDP (UdpPacket.buildCommonPart + buildIPv4UdpPacket / buildIPv6UdpPacket, UdpPacket.java:68-124):
+ *     sport, dport, length 8 + data_len, the UDP sum over the pseudo-header (protocol 17, length 8 +
+ *     data_len), the header and the payload -- A COMPUTED 0x0000 IS STORED AS 0xffff --, the data_len
+ *     payload bytes from d_src + data_off.
+ * A record is refused -- d_frame_len[i] 0, d_out[i] 0, S_BAD_DESC, not one byte written, nothing read
+ * but the record and its template -- when hdr >= n_hdr; the template's l3_ver is not 4 / 6, its l2_len
+ * not 0 / 14, its bytes 52..57 or its rsv not 0; the record's rsv != 0; 28 + data_len (IPv4) or 8 +
+ * data_len (IPv6) > 65535 (Java would silently truncate both length fields: the build refuses);
+ * L > frame_cap; frame_off + L > dst_len or data_off + data_len > src_len (both checked without
+ * wrapping).  Otherwise d_frame_len[i] = L (required), d_out[i] (may be NULL) holds the IPv4 header
+ * sum in bits 0..15 (0 for IPv6) and the stored UDP field in bits 16..31, d_status[i] (may be NULL)
+ * S_DONE.  Alignment, the limit on n, n == 0 and the no-overlap rule are vpcsum_tcp_build_async's. */
+int vpcsum_udp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_src, uint64_t src_len,
+                           const vpcsum_udphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_udpdg_t* d_dg, uint32_t n,
+                           uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream);
+
+/* UDP receive (additive, the ABI version stays 4): the build's mirror, the TCP receive for datagrams.
+ * What UdpInput.handle does on the host for every datagram of a listening socket --
+ * receivingQueue.store(src, port, udpPkt.getData().getRawPacket(0)), UdpInput.java:44-68;
+ * ReceivingQueue.store's data.copy(), UdpListenEntry.java:51-65 -- fused into the ingress verify: the
+ * segment is read once, its UDP sum recomputed and compared, and the data bytes stored from the
+ * registers that summed them.  This call REPLACES vpcsum_compute_async / VPCSUM_MODE_VERIFY for the
+ * frames it is given.  THE BYTES ARE STORED WHATEVER THE VERDICT, as in the TCP receive: the caller
+ * enqueues the datagram only on the verdict its csum-recalc policy accepts; the source address and
+ * port of the Datagram come from the parse's vpcsum_tuple_t. */
+#define VPCSUM_UDPRX_STORE 0x01u
+typedef struct vpcsum_udprx {   /* one per descriptor; 16 bytes, 8-byte aligned */
+    uint64_t dst_off;  /* where data byte 0 goes in the receive arena, any alignment */
+    uint32_t dst_cap;  /* room at dst_off; a datagram that needs more is refused */
+    uint8_t  ops;      /* VPCSUM_UDPRX_STORE, or 0: verify only */
+    uint8_t  rsv[3];   /* must be 0 */
+} vpcsum_udprx_t;
+
+/* Descriptor i (as vpcsum_parse_ether_async writes them) pairs with record i.  With seg_len = l3_len -
+ * l4_off, a record that is not refused gets
+ *   d_status[i], d_out[i] (each may be NULL): exactly what vpcsum_compute_async writes for the
+ *     descriptor with VPCSUM_MODE_VERIFY -- S_DONE; the recomputed sum with a computed 0 as 0xffff;
+ *     S_L4_OK iff the stored field equals it (so a stored 0xffff on a datagram whose sum computes to 0
+ *     is OK); S_UDP_NOCSUM, and never S_L4_OK, for a stored 0; S_IP_OK iff the descriptor has F_IP and
+ *     the IPv4 header sum matches;
+ *   with VPCSUM_UDPRX_STORE: segment bytes [8, seg_len) at d_dst + dst_off and d_stored[i] (required)
+ *     = seg_len - 8; without it d_stored[i] = 0 and d_dst is not written.
+ * The UDP length field is summed and not consulted: UdpInput parses with initPartial(
+ * LEVEL_HANDLED_FIELDS), whose data is bytes.sub(8, bytes.length() - 8) of the IP-truncated buffer
+ * (UdpPacket.java:30-38); only the full from() compares the field.  L2 padding after l3_len is neither
+ * read, summed nor stored.  No byte outside [dst_off, dst_off + stored) is written.  A record is
+ * refused -- d_stored[i] 0, d_out[i] 0, S_BAD_DESC, not one byte written to d_dst, nothing of the
+ * arena read -- when l4_proto != 17; l3_ver is not 4 / 6; the descriptor lacks F_L4 or carries F_L4P,
+ * F_RAW or F_PRE; F_IP on IPv6; l4_off > l3_len, or an l4_off vpcsum_compute_async refuses (IPv4:
+ * below 20 or not a multiple of 4; IPv6: below 40); l3_off + l3_len > arena_len (checked without
+ * wrapping); seg_len < 8; ops & ~VPCSUM_UDPRX_STORE or rsv != 0; with STORE, seg_len - 8 > dst_cap or
+ * dst_off + stored > dst_len (without wrapping).  seg_len == 8 is legal and stores 0 bytes.
+ * Alignment, the limit on n, n == 0 and the no-overlap rule are vpcsum_tcp_recv_async's. */
+int vpcsum_udp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc,
+                          const vpcsum_udprx_t* d_rx, uint32_t n, uint8_t* d_dst, uint64_t dst_len,
+                          uint32_t* d_stored, uint32_t* d_out, uint8_t* d_status, void* stream);
+
 /* Streaming-read ceiling probe: reads `bytes` from d_buf with 16-B lanes, writes one word per
  * block into d_sink.  Used by bench.py to report a measured HBM read roof next to 8 TB/s. */
 int vpcsum_read_probe_async(const uint8_t* d_buf, uint64_t bytes, uint32_t* d_sink,
@@ -797,6 +889,26 @@ int vpcsum_ctx_recv_tcp_frames(vpcsum_ctx_t* ctx, const uint8_t* h_arena, uint64
                                const vpcsum_desc_t* h_desc, const vpcsum_tcprx_t* h_rx, uint32_t n,
                                uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored, uint32_t* h_out,
                                uint8_t* h_status, uint64_t* ticket);
+/* vpcsum_udp_build_async from host memory, in one submission, by vpcsum_ctx_build_tcp_frames' plan:
+ * h_dst must be inside a REGISTERED arena (an unregistered destination is refused); a registered
+ * h_src is read in place, any other is staged as the one span of the batch's payloads (refused if
+ * larger than the context's max_arena_bytes), data_off rebased in the library's own copy of the
+ * records.  n and n_hdr are each at most the context's max_pkts.  At vpcsum_ctx_wait h_frame_len[i]
+ * (required), h_out[i] and h_status[i] (each may be NULL) hold what vpcsum_udp_build_async writes.
+ * Always launched: no service-grid, device-group or process-wide form. */
+int vpcsum_ctx_build_udp_frames(vpcsum_ctx_t* ctx, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
+                                const vpcsum_udphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_udpdg_t* h_dg, uint32_t n,
+                                uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket);
+/* vpcsum_udp_recv_async from host memory, in one submission, by vpcsum_ctx_recv_tcp_frames' plan:
+ * h_dst must be inside a REGISTERED arena (an unregistered destination is refused); a registered
+ * h_arena (the RX umem) is read in place, any other is staged exactly as vpcsum_ctx_submit stages
+ * it.  n is at most the context's max_pkts.  At vpcsum_ctx_wait h_stored[i] (required), h_out[i] and
+ * h_status[i] (each may be NULL) hold what vpcsum_udp_recv_async writes, and the data bytes are in
+ * h_dst whatever the verdict.  Always launched: no service-grid, device-group or process-wide form. */
+int vpcsum_ctx_recv_udp_frames(vpcsum_ctx_t* ctx, const uint8_t* h_arena, uint64_t arena_len,
+                               const vpcsum_desc_t* h_desc, const vpcsum_udprx_t* h_rx, uint32_t n,
+                               uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored, uint32_t* h_out,
+                               uint8_t* h_status, uint64_t* ticket);
 /* The egress flush of a batch holding NAT'd frames: vpcsum_ctx_submit where
  * descriptors with VPCSUM_F_PRE take their L4 sum from h_pre[i] (pre_fmt as vpcsum_pre_async;
  * entries of other descriptors are ignored) and the others are summed in full, in one submission.
@@ -980,6 +1092,18 @@ int Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts(PNIEnv_vpcsum_long* env, int64_t
  *                      MemorySegment dst, long dstLen, MemorySegment stored, MemorySegment out,
  *                      MemorySegment status) -> long ticket (vpcsum_ctx_recv_tcp_frames) */
 int Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
+                                               void* rx, int32_t n, void* dst, int64_t dstLen, void* stored, void* out,
+                                               void* status);
+/* VPCsum.buildUdpFrames(long ctx, MemorySegment dst, long dstLen, MemorySegment src, long srcLen,
+ *                       MemorySegment hdr, int nHdr, MemorySegment dg, int n, MemorySegment frameLen,
+ *                       MemorySegment out, MemorySegment status) -> long ticket (vpcsum_ctx_build_udp_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
+                                                int64_t srcLen, void* hdr, int32_t nHdr, void* dg, int32_t n,
+                                                void* frameLen, void* out, void* status);
+/* VPCsum.recvUdpFrames(long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment rx, int n,
+ *                      MemorySegment dst, long dstLen, MemorySegment stored, MemorySegment out,
+ *                      MemorySegment status) -> long ticket (vpcsum_ctx_recv_udp_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
                                                void* rx, int32_t n, void* dst, int64_t dstLen, void* stored, void* out,
                                                void* status);
 /* VPCsum.setService(long ctx, int idleUs) */

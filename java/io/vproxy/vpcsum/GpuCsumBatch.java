@@ -454,6 +454,39 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * The datagrams of a UDP socket (UdpOutput.sendUdp's loop over sendingQueue.fetch()) built on the
+     * GPU straight into TX chunks of the umem: {@code count} records ({@link VPCsum#udpDg}) over
+     * {@code nHdr} templates ({@link VPCsum#tcpHdr} with ack and window 0: one per EnhancedUDPEntry),
+     * payloads read from {@code sendBuf}.  Fills {@code frameLenOut} (u32 per record): the frame's
+     * length for the TX descriptor, or 0 -- the record was refused, build that datagram on the host.
+     * Needs a library with the entry ({@code VPCsumLib.hasUdp()}).
+     */
+    public MemorySegment buildUdp(MemorySegment sendBuf, long sendBufLen, MemorySegment hdr, int nHdr, MemorySegment dg, int count,
+                                  MemorySegment frameLenOut, MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().buildUdpFrames(env, ctx, umem, umemLen, sendBuf, sendBufLen, hdr, nHdr, dg, count, frameLenOut,
+            MemorySegment.NULL, statusOut);
+        VPCsum.get().waitFor(env, ctx, t);
+        return frameLenOut;
+    }
+
+    /**
+     * The datagrams a listening UDP socket receives (UdpInput.handle -> receivingQueue.store):
+     * {@code count} frames of the umem described in {@code frameDesc} (the parse's descriptors), one
+     * record each in {@code rx} ({@link VPCsum#udpRx}), verified and their data stored into
+     * {@code recvBuf} -- a registered arena -- in one pass.  Replaces {@link #verify} for these
+     * frames.  Fills {@code storedOut} (u32 per record) and {@code statusOut}; the caller builds the
+     * Datagram (source from the parse's tuple) only on the verdict its csum-recalc policy accepts:
+     * the bytes are stored whatever the verdict.  Needs {@code VPCsumLib.hasUdp()}.
+     */
+    public MemorySegment recvUdp(MemorySegment frameDesc, MemorySegment rx, int count, MemorySegment recvBuf, long recvBufLen,
+                                 MemorySegment storedOut, MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().recvUdpFrames(env, ctx, umem, umemLen, frameDesc, rx, count, recvBuf, recvBufLen, storedOut,
+            MemorySegment.NULL, statusOut);
+        VPCsum.get().waitFor(env, ctx, t);
+        return storedOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

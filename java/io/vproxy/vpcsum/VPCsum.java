@@ -226,6 +226,38 @@ public class VPCsum {
         rx.set(java.lang.foreign.ValueLayout.JAVA_BYTE, off + 15, (byte) 0);
     }
 
+    /** bytes of one vpcsum_udpdg_t datagram record ({@link #udpDg}) */
+    public static final int UDP_DG = 32;
+    /** bytes of one vpcsum_udprx_t receive record ({@link #udpRx}) */
+    public static final int UDP_RX = 16;
+    /** vpcsum_udprx_t.ops: store the datagram's data; 0: verify only */
+    public static final int UDPRX_STORE = 0x01;
+
+    /** Fill the 32-byte record at {@code dg[off..]} for one datagram of UdpOutput.sendUdp's loop: the
+     * frame goes to {@code frameOff} of the destination arena (room {@code frameCap} there), its
+     * {@code dataLen} bytes (Datagram.data; 0 is legal) come from {@code dataOff} of the source arena,
+     * {@code hdrIndex} names the template ({@link #tcpHdr} with ack 0 and window 0: src / sport from
+     * udp.listening, dst / dport from the datagram's remote). */
+    public static void udpDg(MemorySegment dg, long off, long frameOff, long dataOff, int hdrIndex, int frameCap, int dataLen) {
+        final var LE = java.nio.ByteOrder.LITTLE_ENDIAN;
+        dg.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off, frameOff);
+        dg.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off + 8, dataOff);
+        dg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 16, hdrIndex);
+        dg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 20, frameCap);
+        dg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 24, dataLen);
+        dg.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 28, 0);
+    }
+
+    /** Fill the 16-byte receive record at {@code rx[off..]} for one received datagram: its data (segment
+     * bytes 8 on) goes to {@code dstOff} of the receive arena, which has room {@code dstCap} there;
+     * {@code store} false: verify only (a datagram ReceivingQueue.store's connect filter drops). */
+    public static void udpRx(MemorySegment rx, long off, long dstOff, int dstCap, boolean store) {
+        final var LE = java.nio.ByteOrder.LITTLE_ENDIAN;
+        rx.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off, dstOff);
+        rx.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 8, dstCap);
+        rx.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 12, store ? UDPRX_STORE : 0);   // ops, rsv[3] 0
+    }
+
     /** Fields of the 16-byte digest at {@code info[off..]} (vpcsum_tcp_digest_async): seq and ack as
      * TcpPacket.getSeqNum / getAckNum return them (unsigned, in a long), window, payload length,
      * header length (0: no record, the descriptor was refused) and flags. */
@@ -762,6 +794,80 @@ public class VPCsum {
         int ERR;
         try {
             ERR = (int) recvTcpFramesMH.invokeExact(ENV.MEMORY, ctx, arena, arenaLen, desc, rx, n, dst, dstLen, stored, out, status);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    /* The UDP pair: resolved on first use, as buildTcpBursts is (VPCsumLib.hasUdp). */
+    private static volatile MethodHandle buildUdpFramesMH;
+    private static volatile MethodHandle recvUdpFramesMH;
+
+    /** The UDP datagram build (vpcsum_ctx_build_udp_frames): {@link #buildTcpFrames} for the datagrams
+     * of UdpOutput.sendUdp, one record of {@link #UDP_DG} bytes ({@link #udpDg}) each.  A UDP sum that
+     * computes to 0 is stored as 0xffff, as UdpPacket does.  After {@link #waitFor}: frameLen[i] (u32)
+     * the frame's length, 0 for a refused record (status[i] S_BAD_DESC, nothing written); out / status
+     * may be MemorySegment.NULL. */
+    public long buildUdpFrames(PNIEnv ENV, long ctx, MemorySegment dst, long dstLen, MemorySegment src, long srcLen,
+                               MemorySegment hdr, int nHdr, MemorySegment dg, int n, MemorySegment frameLen, MemorySegment out,
+                               MemorySegment status) throws java.io.IOException {
+        MethodHandle MH = buildUdpFramesMH;
+        if (MH == null) {
+            if (!VPCsumLib.hasUdp()) {
+                throw new java.io.IOException("libvpcsum has no buildUdpFrames: the library is older than this binding");
+            }
+            MH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+                "Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames", long.class /* ctx */, MemorySegment.class /* dst */,
+                long.class /* dstLen */, MemorySegment.class /* src */, long.class /* srcLen */, MemorySegment.class /* hdr */,
+                int.class /* nHdr */, MemorySegment.class /* dg */, int.class /* n */, MemorySegment.class /* frameLen */,
+                MemorySegment.class /* out */, MemorySegment.class /* status */);
+            buildUdpFramesMH = MH;
+        }
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) MH.invokeExact(ENV.MEMORY, ctx, dst, dstLen, src, srcLen, hdr, nHdr, dg, n, frameLen, out, status);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    /** The UDP receive (vpcsum_ctx_recv_udp_frames): {@link #recvTcpFrames} for datagrams, one record
+     * of {@link #UDP_RX} bytes ({@link #udpRx}) per descriptor.  status[i] is the verify status --
+     * S_UDP_NOCSUM for a stored 0, S_L4_OK for a stored 0xffff whose sum computes to 0 -- or S_BAD_DESC
+     * for a refused record; stored[i] (u32) the data bytes, segment bytes 8 on whatever the UDP length
+     * field says (UdpPacket.initPartial).  THE BYTES ARE STORED WHATEVER THE VERDICT: enqueue the
+     * Datagram only on the verdict the csum-recalc policy accepts, with the source address and port of
+     * the parse's tuple. */
+    public long recvUdpFrames(PNIEnv ENV, long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment rx, int n,
+                              MemorySegment dst, long dstLen, MemorySegment stored, MemorySegment out, MemorySegment status)
+        throws java.io.IOException {
+        MethodHandle MH = recvUdpFramesMH;
+        if (MH == null) {
+            if (!VPCsumLib.hasUdp()) {
+                throw new java.io.IOException("libvpcsum has no recvUdpFrames: the library is older than this binding");
+            }
+            MH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+                "Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames", long.class /* ctx */, MemorySegment.class /* arena */,
+                long.class /* arenaLen */, MemorySegment.class /* desc */, MemorySegment.class /* rx */, int.class /* n */,
+                MemorySegment.class /* dst */, long.class /* dstLen */, MemorySegment.class /* stored */,
+                MemorySegment.class /* out */, MemorySegment.class /* status */);
+            recvUdpFramesMH = MH;
+        }
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) MH.invokeExact(ENV.MEMORY, ctx, arena, arenaLen, desc, rx, n, dst, dstLen, stored, out, status);
         } catch (Throwable THROWABLE) {
             throw PanamaUtils.convertInvokeExactException(THROWABLE);
         }

@@ -56,6 +56,12 @@ final class VPCsumLib {
         return has("Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts");
     }
 
+    /** The UDP datagram build and receive ({@link VPCsum#buildUdpFrames}, {@link VPCsum#recvUdpFrames},
+     * {@link GpuCsumBatch#buildUdp}, {@link GpuCsumBatch#recvUdp}). */
+    static boolean hasUdp() {
+        return has("Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames") && has("Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames");
+    }
+
     /** IOException unless the loaded library speaks ABI {@code expected} (VPCsum.ABI_VERSION). */
     static void requireAbi(int expected) throws IOException {
         int v = abiVersion();

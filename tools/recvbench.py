@@ -13,7 +13,9 @@ window.  Timed with events over --launches launches after a warm-up, legs in alt
 a, b and c use only entry points and kernels that this tool's library shares with its parent.
 Algorithmic bytes per frame: the segment read + data_len written + descriptor and record.  Before
 timing, r's receive buffer is compared with b's and with the send buffer, r's status and out with a's.
-Prints one JSON line.  usage: recvbench.py [frames] [--launches N]"""
+With --udp only the UDP leg runs: vpcsum_udp_recv_async (k_udp_recv) on datagrams of 1,360 and 1,472
+payload bytes, timed against leg r on segments of the same payload and against leg c, in the same run.
+Prints one JSON line.  usage: recvbench.py [frames] [--launches N] [--udp]"""
 import ctypes
 import json
 import os
@@ -67,6 +69,66 @@ hdr["src"][0, :4], hdr["dst"][0, :4] = (10, 0, 0, 1), (10, 0, 0, 2)
 hdr["sport"], hdr["dport"] = np.frombuffer((43210).to_bytes(2, "big"), np.uint8), np.frombuffer((443).to_bytes(2, "big"), np.uint8)
 hdr["ack"], hdr["window"] = np.frombuffer((0x01020304).to_bytes(4, "big"), np.uint8), np.frombuffer((65535).to_bytes(2, "big"), np.uint8)
 d_hdr = dev(hdr)
+
+def udp_leg():
+    """--udp: vpcsum_udp_recv_async (k_udp_recv) on datagrams of 1,360 and 1,472 payload bytes, against
+    k_tcp_recv on segments of the same payload and a contiguous copy of the same bytes, in the same run."""
+    uh = hdr.copy()
+    uh["ack"], uh["window"] = 0, 0
+    d_uh = dev(uh)
+    r_all = {"frames_per_batch": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
+             "frames": "Ethernet / IPv4 / UDP against Ethernet / IPv4 / TCP of the same payload"}
+    for data_len in (1360, 1472):
+        off = np.arange(n, dtype=np.uint64)
+        dg, seg = np.zeros(n, V.UDPDG_DTYPE), np.zeros(n, V.TCPSEG_DTYPE)
+        for rec in (dg, seg):
+            rec["frame_off"], rec["data_off"] = off * STRIDE + HEADROOM, off * data_len
+            rec["frame_cap"], rec["data_len"] = STRIDE - HEADROOM, data_len
+        seg["flags"] = 0x18
+        g = torch.Generator(device="cuda").manual_seed(data_len)
+        sent = torch.randint(0, 256, (n * data_len,), dtype=torch.uint8, device="cuda", generator=g)
+        fr_u, fr_t = (torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda") for _ in range(2))
+        flen_u, flen_t = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+        V.udp_build(fr_u, sent, d_uh, 1, dev(dg), n, flen_u, None, None)
+        V.tcp_build(fr_t, sent, d_hdr, 1, dev(seg), n, flen_t, None, None)
+        foff = dev(dg["frame_off"].copy())
+        desc_u, desc_t = (torch.zeros(n * 16, dtype=torch.uint8, device="cuda") for _ in range(2))
+        V.parse_ether(fr_u, foff, flen_u, n, desc_u)
+        V.parse_ether(fr_t, foff, flen_t, n, desc_t)
+        urx, trx = np.zeros(n, V.UDPRX_DTYPE), np.zeros(n, V.TCPRX_DTYPE)
+        for rec, store in ((urx, V.UDPRX_STORE), (trx, V.TCPRX_STORE)):
+            rec["dst_off"], rec["dst_cap"], rec["ops"] = off * data_len, data_len, store
+        d_urx, d_trx = dev(urx), dev(trx)
+        rb_u, rb_t, copy = (torch.zeros(n * data_len, dtype=torch.uint8, device="cuda") for _ in range(3))
+        stored, out = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+        st = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        legs = {"u_udp_recv": lambda: V.udp_recv(fr_u, desc_u, d_urx, n, rb_u, stored, out, st),
+                "r_tcp_recv": lambda: V.tcp_recv(fr_t, desc_t, d_trx, n, rb_t, stored, out, st),
+                "c_contiguous_copy": lambda: copy.copy_(sent)}
+        legs["u_udp_recv"]()
+        torch.cuda.synchronize()
+        assert int((st != (V.S_DONE | V.S_IP_OK | V.S_L4_OK)).sum().item()) == 0 and int((stored != data_len).sum().item()) == 0
+        assert torch.equal(rb_u, sent), "u stores the sent bytes"
+        us = {k: [] for k in legs}
+        for _ in range(rounds):
+            for k, fn in legs.items():
+                us[k].append(round(timed(fn), 2))
+        assert torch.equal(rb_u, sent) and torch.equal(rb_t, sent)
+        r = {"udp_frame_len": 42 + data_len, "tcp_frame_len": 54 + data_len}
+        for k, v in us.items():
+            r[k] = {"us_rounds": v, "us_median": sorted(v)[len(v) // 2]}
+        r["u_over_r"] = round(r["u_udp_recv"]["us_median"] / r["r_tcp_recv"]["us_median"], 4)
+        r["u_over_c"] = round(r["u_udp_recv"]["us_median"] / r["c_contiguous_copy"]["us_median"], 3)
+        r["r_round_spread"] = round(max(us["r_tcp_recv"]) / min(us["r_tcp_recv"]) - 1, 4)
+        r["u_round_spread"] = round(max(us["u_udp_recv"]) / min(us["u_udp_recv"]) - 1, 4)
+        r_all[f"data_len_{data_len}"] = r
+        del sent, fr_u, fr_t, rb_u, rb_t, copy
+    print(json.dumps(r_all))
+
+
+if "--udp" in sys.argv:
+    udp_leg()
+    sys.exit(0)
 
 res = {"frames_per_batch": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
        "frames": "Ethernet / IPv4 / TCP, PSH|ACK, no options"}

@@ -144,6 +144,11 @@ def main(tag):
         if d:
             json.dump({"src_hash": prov["src_hash"], "head": prov["head"], **d},
                       open(os.path.join(P, f"{tag}_{out}.json"), "w"), indent=1)
+    for f in sorted(glob.glob(os.path.join(G, f"{tag}_udp_*bench_*.log"))):   # tools/segbench.py / recvbench.py --udp, one log per process
+        d = json_line(f)
+        if d:
+            json.dump({"src_hash": prov["src_hash"], "head": prov["head"], **d},
+                      open(os.path.join(P, os.path.basename(f)[:-4] + ".json"), "w"), indent=1)
     vm = sorted(glob.glob(os.path.join(G, f"{tag}_vm_*.log")))   # tools/verify_modes.sh logs
     if vm:
         dst = os.path.join(P, f"{tag}_verify_modes")

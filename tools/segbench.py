@@ -14,7 +14,9 @@ over --launches launches after a warm-up, legs in alternating rounds:
      the same process
 Algorithmic bytes per segment: data_len read + L written + the 32-byte record.  Before timing, b's
 and s's frames are compared with a's: all must build the same bytes.
-Prints one JSON line.  usage: segbench.py [segments] [--launches N] [--lib libvpcsum.so]
+With --udp only the UDP leg runs: vpcsum_udp_build_async (k_udp_build) on datagrams of 1,360 and 1,472
+payload bytes, timed against leg a on segments of the same payload and against leg d, in the same run.
+Prints one JSON line.  usage: segbench.py [segments] [--launches N] [--lib libvpcsum.so] [--udp]
 (--lib: another build of the library, e.g. one compiled with -DVPCSUM_BURST_BINARY_SEARCH)"""
 import ctypes
 import json
@@ -71,6 +73,55 @@ hdr["src"][0, :4], hdr["dst"][0, :4] = (10, 0, 0, 1), (10, 0, 0, 2)
 hdr["sport"], hdr["dport"] = np.frombuffer((43210).to_bytes(2, "big"), np.uint8), np.frombuffer((443).to_bytes(2, "big"), np.uint8)
 hdr["ack"], hdr["window"] = np.frombuffer((0x01020304).to_bytes(4, "big"), np.uint8), np.frombuffer((65535).to_bytes(2, "big"), np.uint8)
 d_hdr = dev(hdr)
+
+def udp_leg():
+    """--udp: vpcsum_udp_build_async (k_udp_build) on datagrams of 1,360 and 1,472 payload bytes, against
+    k_tcp_build on segments of the same payload and a contiguous copy of the same bytes, in the same run."""
+    uh = hdr.copy()
+    uh["ack"], uh["window"] = 0, 0
+    d_uh = dev(uh)
+    r_all = {"datagrams": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
+             "frames": "Ethernet / IPv4 / UDP against Ethernet / IPv4 / TCP of the same payload"}
+    for data_len in (1360, 1472):
+        off = np.arange(n, dtype=np.uint64)
+        dg, seg = np.zeros(n, V.UDPDG_DTYPE), np.zeros(n, V.TCPSEG_DTYPE)
+        for rec in (dg, seg):
+            rec["frame_off"], rec["data_off"] = off * STRIDE + HEADROOM, off * data_len
+            rec["frame_cap"], rec["data_len"] = STRIDE - HEADROOM, data_len
+        seg["flags"] = 0x18
+        d_dg, d_seg = dev(dg), dev(seg)
+        g = torch.Generator(device="cuda").manual_seed(data_len)
+        src = torch.randint(0, 256, (n * data_len,), dtype=torch.uint8, device="cuda", generator=g)
+        dst_u, dst_t = (torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda") for _ in range(2))
+        flen, out = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+        st = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        flat = torch.empty_like(src)
+        legs = {"u_udp_build": lambda: V.udp_build(dst_u, src, d_uh, 1, d_dg, n, flen, out, st),
+                "a_tcp_build": lambda: V.tcp_build(dst_t, src, d_hdr, 1, d_seg, n, flen, out, st),
+                "d_contiguous_copy": lambda: flat.copy_(src)}
+        legs["u_udp_build"]()
+        torch.cuda.synchronize()
+        assert int((st != V.S_DONE).sum().item()) == 0 and int((flen != 42 + data_len).sum().item()) == 0
+        assert torch.equal(dst_u.view(n, STRIDE)[:, HEADROOM + 42:HEADROOM + 42 + data_len].reshape(-1), src), "the payloads arrive"
+        us = {k: [] for k in legs}
+        for _ in range(rounds):
+            for k, fn in legs.items():
+                us[k].append(round(timed(fn), 2))
+        r = {"udp_frame_len": 42 + data_len, "tcp_frame_len": 54 + data_len}
+        for k, v in us.items():
+            r[k] = {"us_rounds": v, "us_median": sorted(v)[len(v) // 2]}
+        r["u_over_a"] = round(r["u_udp_build"]["us_median"] / r["a_tcp_build"]["us_median"], 4)
+        r["u_over_d"] = round(r["u_udp_build"]["us_median"] / r["d_contiguous_copy"]["us_median"], 3)
+        r["a_round_spread"] = round(max(us["a_tcp_build"]) / min(us["a_tcp_build"]) - 1, 4)
+        r["u_round_spread"] = round(max(us["u_udp_build"]) / min(us["u_udp_build"]) - 1, 4)
+        r_all[f"data_len_{data_len}"] = r
+        del src, dst_u, dst_t, flat
+    print(json.dumps(r_all))
+
+
+if "--udp" in sys.argv:
+    udp_leg()
+    sys.exit(0)
 
 res = {"segments": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
        "frames": "Ethernet / IPv4 / TCP, PSH|ACK"}

@@ -28,6 +28,8 @@
 #include "tcp_build.h"
 #include "tcp_burst.h"
 #include "tcp_recv.h"
+#include "udp_build.h"
+#include "udp_recv.h"
 #include "vpcsum.h"
 
 namespace vpcsum {
@@ -201,10 +203,10 @@ struct Slot {
     Mapped<uint8_t> h_verdict;         // and its verdicts
     DeviceOnly<vpcsum_fastpath_t> d_fp;   // a forwarding flow batch's Fastpath records (lookup -> L2 write)
     Mapped<uint32_t> h_port;           // and its output ports
-    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records, templates and frame lengths
+    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records (a UDP build batch's: the same 32 B), templates and frame lengths
     Mapped<vpcsum_tcphdr_t> h_thdr;
     Mapped<uint32_t> h_tlen;           // (a TCP receive batch's stored counts too)
-    Mapped<vpcsum_tcprx_t> h_trx;      // a TCP receive batch's records
+    Mapped<vpcsum_tcprx_t> h_trx;      // a TCP receive batch's records (a UDP receive batch's: the same 16 B)
     Mapped<vpcsum_tcpburst_t> h_tburst;   // a TCP burst batch's records (its frame table: h_foff)
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
@@ -1637,6 +1639,98 @@ static int flowtab_push(vpcsum_flowtab* f, FlowDirty& dirty, std::vector<uint32_
     return 0;
 }
 
+// The segment / datagram build of host memory (vpcsum_ctx_build_tcp_frames, vpcsum_ctx_build_udp_frames):
+// frames written in place into a registered destination, the payloads read in place from a registered
+// source or staged as one span.  Always launched (the service grid has no build), on the slot's one
+// stream.  Rec: vpcsum_tcpseg_t or vpcsum_udpdg_t, both 32 B, whose copy lies in the slot's one pinned
+// record buffer (h_tseg); `launch`: the kernel's, on the device addresses.
+template <class Rec, class Launch>
+static int ctx_build_frames(vpcsum_ctx_t* c, const char* what, const char* launch_what, uint8_t* h_dst, uint64_t dst_len,
+                            const uint8_t* h_src, uint64_t src_len, const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr,
+                            const Rec* h_rec, uint32_t n, uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status,
+                            uint64_t* ticket, Launch launch) {
+    static_assert(sizeof(Rec) == sizeof(vpcsum_tcpseg_t) && alignof(Rec) == alignof(vpcsum_tcpseg_t), "one record buffer for both");
+    if (!c || !ticket) return fail("%s: NULL context or ticket", what);
+    if (n > c->max_pkts) return fail("%s: %u records > capacity %u", what, n, c->max_pkts);
+    if (n_hdr > c->max_pkts) return fail("%s: %u templates > capacity %u", what, n_hdr, c->max_pkts);
+    if (n && (!h_dst || !h_rec || !h_frame_len || (!h_hdr && n_hdr) || (!h_src && src_len)))
+        return fail("%s: NULL destination, source, templates, records or frame lengths", what);
+    std::lock_guard<std::mutex> lk(c->mu);
+    VPC_ON_DEVICE(c->device);
+    uint8_t* base = n ? mapped_dev(c, h_dst, dst_len) : nullptr;
+    if (n && !base) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
+    // the source: read in place when registered, else the span of the payloads that lie inside it
+    const uint8_t* src_dev = n && src_len ? mapped_dev(c, h_src, src_len) : nullptr;
+    const bool staged = n && src_len && !src_dev;
+    TcpPayloadSpan sp = {0, 0};
+    if (staged && !tcp_build_payload_span(h_rec, n, src_len, c->max_arena, &sp))
+        return fail("%s: the payloads span %llu bytes > capacity %llu", what, (unsigned long long)sp.len,
+                    (unsigned long long)c->max_arena);
+    Batch b;
+    Slot* slot = slot_acquire(c, &b.ticket);
+    if (!slot) return -1;
+    Slot& s = *slot;
+    b.n = n;
+    b.zero_copy = true;   // the frames are written in place through the destination's mapping
+    if (n) {
+        // records, templates and frame lengths: pinned
+        if (slot_scratch(c, what, s.h_tseg, s.h_thdr, s.h_tlen) != 0) return -1;
+        b.hand_back({status_of(c, s, false, h_status, n), {h_frame_len, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
+        memcpy(s.h_tseg.p, h_rec, (size_t)n * sizeof(Rec));
+        if (n_hdr) memcpy(s.h_thdr.p, h_hdr, (size_t)n_hdr * sizeof(vpcsum_tcphdr_t));
+        if (staged) {
+            // the library's copy of the records names the staged span
+            tcp_build_rebase_payloads(reinterpret_cast<Rec*>(s.h_tseg.p), n, src_len, sp.lo);
+            if (sp.len) memcpy(s.h_arena.p, h_src + sp.lo, sp.len);   // pageable -> pinned staging
+            if (stage_frames_up(s, sp.len) != 0) return -1;
+        }
+        VPC_CHECK(launch(base, dst_len, staged ? s.d_arena.p : src_dev, staged ? sp.len : src_len, s.h_thdr.dev, n_hdr,
+                         reinterpret_cast<const Rec*>(s.h_tseg.dev), n, s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev,
+                         s.stream),
+                  launch_what);
+    }
+    return slot_commit(s, b, ticket);
+}
+
+// The TCP / UDP receive of host memory (vpcsum_ctx_recv_tcp_frames, vpcsum_ctx_recv_udp_frames):
+// payloads written in place into a registered destination, the frames read in place from a registered
+// arena or staged by vpcsum_ctx_submit's plan.  Always launched, on the slot's one stream; descriptors,
+// records and results in mapped pinned memory.  Rec: vpcsum_tcprx_t or vpcsum_udprx_t, both 16 B, whose
+// copy lies in the slot's one pinned record buffer (h_trx); `launch`: the kernel's, on the device addresses.
+template <class Rec, class Launch>
+static int ctx_recv_frames(vpcsum_ctx_t* c, const char* what, const char* launch_what, const uint8_t* h_arena, uint64_t arena_len,
+                           const vpcsum_desc_t* h_desc, const Rec* h_rx, uint32_t n, uint8_t* h_dst, uint64_t dst_len,
+                           uint32_t* h_stored, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket, Launch launch) {
+    static_assert(sizeof(Rec) == sizeof(vpcsum_tcprx_t) && alignof(Rec) == alignof(vpcsum_tcprx_t), "one record buffer for both");
+    if (desc_args(c, what, "arena, descriptors or records", h_arena, h_desc, h_rx, n, ticket) != 0) return -1;
+    if (n && (!h_stored || (!h_dst && dst_len))) return fail("%s: NULL destination or stored counts", what);
+    return desc_entry(c, const_cast<uint8_t*>(h_arena), arena_len, h_desc, n, VPCSUM_MODE_VERIFY,
+                      [&](Slot& s, Batch& b, const BatchSpan& sp, uint8_t* base) {
+        uint8_t* dst_dev = n && dst_len ? mapped_dev(c, h_dst, dst_len) : nullptr;
+        if (n && dst_len && !dst_dev) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
+        b.user_arena = nullptr;   // nothing goes back into the frames
+        b.user_desc = nullptr;
+        b.zero_copy = true;       // the payloads are written in place through the destination's mapping
+        if (n) {
+            if (slot_scratch(c, what, s.h_trx, s.h_tlen) != 0) return -1;
+            b.hand_back({status_of(c, s, false, h_status, n), {h_stored, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
+            memcpy(s.h_trx.p, h_rx, (size_t)n * sizeof(Rec));
+            uint64_t dev_len = arena_len;
+            if (base) {
+                memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+            } else {
+                if (stage_desc_frames(c, s, what, h_arena, arena_len, h_desc, n, sp, &dev_len) != 0) return -1;
+                if (stage_frames_up(s, dev_len) != 0) return -1;
+            }
+            VPC_CHECK(launch(base ? base : s.d_arena.p, dev_len, s.h_desc.dev, reinterpret_cast<const Rec*>(s.h_trx.dev), n,
+                             dst_dev, dst_len, s.h_tlen.dev,
+                             h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
+                      launch_what);
+        }
+        return slot_commit(s, b, ticket);
+    });
+}
+
 extern "C" {
 
 int vpcsum_flowtab_create(int device, uint32_t max_flows, vpcsum_flowtab_t** out) {
@@ -1854,6 +1948,48 @@ int vpcsum_tcp_digest_async(const uint8_t* d_arena, uint64_t arena_len, const vp
     } VPC_CATCH("vpcsum_tcp_digest_async")
 }
 
+int vpcsum_udp_build_async(uint8_t* d_dst, uint64_t dst_len, const uint8_t* d_src, uint64_t src_len,
+                           const vpcsum_udphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_udpdg_t* d_dg, uint32_t n,
+                           uint32_t* d_frame_len, uint32_t* d_out, uint8_t* d_status, void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_dst) return fail("vpcsum_udp_build_async: NULL destination arena");
+        if (!d_src && src_len) return fail("vpcsum_udp_build_async: NULL source arena");
+        if (!d_hdr && n_hdr) return fail("vpcsum_udp_build_async: NULL templates");
+        if (!d_dg) return fail("vpcsum_udp_build_async: NULL records");
+        if (!d_frame_len) return fail("vpcsum_udp_build_async: NULL frame lengths");
+        if ((uintptr_t)d_dg & 7) return fail("vpcsum_udp_build_async: records not 8-byte aligned");
+        if ((uintptr_t)d_hdr & 3) return fail("vpcsum_udp_build_async: templates not 4-byte aligned");
+        if ((uintptr_t)d_frame_len & 3) return fail("vpcsum_udp_build_async: frame lengths not 4-byte aligned");
+        if ((uintptr_t)d_out & 3) return fail("vpcsum_udp_build_async: out words not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_udp_build_async: %u records > 2^28", n);
+        VPC_CHECK(launch_udp_build(d_dst, dst_len, d_src, src_len, d_hdr, n_hdr, d_dg, n, d_frame_len, d_out, d_status,
+                                   (hipStream_t)stream),
+                  "UDP build launch");
+        return 0;
+    } VPC_CATCH("vpcsum_udp_build_async")
+}
+
+int vpcsum_udp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, const vpcsum_udprx_t* d_rx,
+                          uint32_t n, uint8_t* d_dst, uint64_t dst_len, uint32_t* d_stored, uint32_t* d_out, uint8_t* d_status,
+                          void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_arena && arena_len) return fail("vpcsum_udp_recv_async: NULL arena");
+        if (!d_desc || !d_rx) return fail("vpcsum_udp_recv_async: NULL descriptors or records");
+        if (!d_dst && dst_len) return fail("vpcsum_udp_recv_async: NULL destination arena");
+        if (!d_stored) return fail("vpcsum_udp_recv_async: NULL stored counts");
+        if (((uintptr_t)d_desc | (uintptr_t)d_rx) & 7) return fail("vpcsum_udp_recv_async: descriptors or records not 8-byte aligned");
+        if ((uintptr_t)d_stored & 3) return fail("vpcsum_udp_recv_async: stored counts not 4-byte aligned");
+        if ((uintptr_t)d_out & 3) return fail("vpcsum_udp_recv_async: out words not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_udp_recv_async: %u records > 2^28", n);
+        VPC_CHECK(launch_udp_recv(d_arena, arena_len, d_desc, d_rx, n, d_dst, dst_len, d_stored, d_out, d_status,
+                                  (hipStream_t)stream),
+                  "UDP receive launch");
+        return 0;
+    } VPC_CATCH("vpcsum_udp_recv_async")
+}
+
 int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream) {
     try {
         if (!f || !n_out) return fail("vpcsum_flowtab_collect: NULL table or count");
@@ -1934,54 +2070,22 @@ int vpcsum_ctx_nat_flow_forward_frames(vpcsum_ctx_t* c, vpcsum_flowtab_t* f, uin
     } VPC_CATCH("vpcsum_ctx_nat_flow_forward_frames")
 }
 
-// The TCP segment build of host memory: frames written in place into a registered destination, the
-// payloads read in place from a registered source or staged as one span.  Always launched (the
-// service grid has no build), on the slot's one stream.
 int vpcsum_ctx_build_tcp_frames(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
                                 const vpcsum_tcphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_tcpseg_t* h_seg, uint32_t n,
                                 uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
-    const char* what = "vpcsum_ctx_build_tcp_frames";
     try {
-        if (!c || !ticket) return fail("%s: NULL context or ticket", what);
-        if (n > c->max_pkts) return fail("%s: %u records > capacity %u", what, n, c->max_pkts);
-        if (n_hdr > c->max_pkts) return fail("%s: %u templates > capacity %u", what, n_hdr, c->max_pkts);
-        if (n && (!h_dst || !h_seg || !h_frame_len || (!h_hdr && n_hdr) || (!h_src && src_len)))
-            return fail("%s: NULL destination, source, templates, records or frame lengths", what);
-        std::lock_guard<std::mutex> lk(c->mu);
-        VPC_ON_DEVICE(c->device);
-        uint8_t* base = n ? mapped_dev(c, h_dst, dst_len) : nullptr;
-        if (n && !base) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
-        // the source: read in place when registered, else the span of the payloads that lie inside it
-        const uint8_t* src_dev = n && src_len ? mapped_dev(c, h_src, src_len) : nullptr;
-        const bool staged = n && src_len && !src_dev;
-        TcpPayloadSpan sp = {0, 0};
-        if (staged && !tcp_build_payload_span(h_seg, n, src_len, c->max_arena, &sp))
-            return fail("%s: the payloads span %llu bytes > capacity %llu", what, (unsigned long long)sp.len,
-                        (unsigned long long)c->max_arena);
-        Batch b;
-        Slot* slot = slot_acquire(c, &b.ticket);
-        if (!slot) return -1;
-        Slot& s = *slot;
-        b.n = n;
-        b.zero_copy = true;   // the frames are written in place through the destination's mapping
-        if (n) {
-            // records, templates and frame lengths: pinned
-            if (slot_scratch(c, what, s.h_tseg, s.h_thdr, s.h_tlen) != 0) return -1;
-            b.hand_back({status_of(c, s, false, h_status, n), {h_frame_len, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
-            memcpy(s.h_tseg.p, h_seg, (size_t)n * sizeof(vpcsum_tcpseg_t));
-            if (n_hdr) memcpy(s.h_thdr.p, h_hdr, (size_t)n_hdr * sizeof(vpcsum_tcphdr_t));
-            if (staged) {
-                // the library's copy of the records names the staged span
-                tcp_build_rebase_payloads(s.h_tseg.p, n, src_len, sp.lo);
-                if (sp.len) memcpy(s.h_arena.p, h_src + sp.lo, sp.len);   // pageable -> pinned staging
-                if (stage_frames_up(s, sp.len) != 0) return -1;
-            }
-            VPC_CHECK(launch_tcp_build(base, dst_len, staged ? s.d_arena.p : src_dev, staged ? sp.len : src_len, s.h_thdr.dev, n_hdr,
-                                       s.h_tseg.dev, n, s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
-                      "TCP build launch");
-        }
-        return slot_commit(s, b, ticket);
+        return ctx_build_frames(c, "vpcsum_ctx_build_tcp_frames", "TCP build launch", h_dst, dst_len, h_src, src_len, h_hdr, n_hdr,
+                                h_seg, n, h_frame_len, h_out, h_status, ticket, launch_tcp_build);
     } VPC_CATCH("vpcsum_ctx_build_tcp_frames")
+}
+
+int vpcsum_ctx_build_udp_frames(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_len, const uint8_t* h_src, uint64_t src_len,
+                                const vpcsum_udphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_udpdg_t* h_dg, uint32_t n,
+                                uint32_t* h_frame_len, uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
+    try {
+        return ctx_build_frames(c, "vpcsum_ctx_build_udp_frames", "UDP build launch", h_dst, dst_len, h_src, src_len, h_hdr, n_hdr,
+                                h_dg, n, h_frame_len, h_out, h_status, ticket, launch_udp_build);
+    } VPC_CATCH("vpcsum_ctx_build_udp_frames")
 }
 
 // The TCP send bursts of host memory: vpcsum_ctx_build_tcp_frames with bursts for records and the
@@ -2038,41 +2142,22 @@ int vpcsum_ctx_build_tcp_bursts(vpcsum_ctx_t* c, uint8_t* h_dst, uint64_t dst_le
     } VPC_CATCH("vpcsum_ctx_build_tcp_bursts")
 }
 
-// The TCP receive of host memory: payloads written in place into a registered destination, the
-// frames read in place from a registered arena or staged by vpcsum_ctx_submit's plan.  Always
-// launched, on the slot's one stream; descriptors, records and results in mapped pinned memory.
 int vpcsum_ctx_recv_tcp_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc,
                                const vpcsum_tcprx_t* h_rx, uint32_t n, uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored,
                                uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
-    const char* what = "vpcsum_ctx_recv_tcp_frames";
     try {
-        if (desc_args(c, what, "arena, descriptors or records", h_arena, h_desc, h_rx, n, ticket) != 0) return -1;
-        if (n && (!h_stored || (!h_dst && dst_len))) return fail("%s: NULL destination or stored counts", what);
-        return desc_entry(c, const_cast<uint8_t*>(h_arena), arena_len, h_desc, n, VPCSUM_MODE_VERIFY,
-                          [&](Slot& s, Batch& b, const BatchSpan& sp, uint8_t* base) {
-            uint8_t* dst_dev = n && dst_len ? mapped_dev(c, h_dst, dst_len) : nullptr;
-            if (n && dst_len && !dst_dev) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
-            b.user_arena = nullptr;   // nothing goes back into the frames
-            b.user_desc = nullptr;
-            b.zero_copy = true;       // the payloads are written in place through the destination's mapping
-            if (n) {
-                if (slot_scratch(c, what, s.h_trx, s.h_tlen) != 0) return -1;
-                b.hand_back({status_of(c, s, false, h_status, n), {h_stored, s.h_tlen.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
-                memcpy(s.h_trx.p, h_rx, (size_t)n * sizeof(vpcsum_tcprx_t));
-                uint64_t dev_len = arena_len;
-                if (base) {
-                    memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
-                } else {
-                    if (stage_desc_frames(c, s, what, h_arena, arena_len, h_desc, n, sp, &dev_len) != 0) return -1;
-                    if (stage_frames_up(s, dev_len) != 0) return -1;
-                }
-                VPC_CHECK(launch_tcp_recv(base ? base : s.d_arena.p, dev_len, s.h_desc.dev, s.h_trx.dev, n, dst_dev, dst_len,
-                                          s.h_tlen.dev, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
-                          "TCP receive launch");
-            }
-            return slot_commit(s, b, ticket);
-        });
+        return ctx_recv_frames(c, "vpcsum_ctx_recv_tcp_frames", "TCP receive launch", h_arena, arena_len, h_desc, h_rx, n, h_dst,
+                               dst_len, h_stored, h_out, h_status, ticket, launch_tcp_recv);
     } VPC_CATCH("vpcsum_ctx_recv_tcp_frames")
+}
+
+int vpcsum_ctx_recv_udp_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc,
+                               const vpcsum_udprx_t* h_rx, uint32_t n, uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored,
+                               uint32_t* h_out, uint8_t* h_status, uint64_t* ticket) {
+    try {
+        return ctx_recv_frames(c, "vpcsum_ctx_recv_udp_frames", "UDP receive launch", h_arena, arena_len, h_desc, h_rx, n, h_dst,
+                               dst_len, h_stored, h_out, h_status, ticket, launch_udp_recv);
+    } VPC_CATCH("vpcsum_ctx_recv_udp_frames")
 }
 
 int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint32_t copy_bytes,
@@ -2765,6 +2850,29 @@ int Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames(PNIEnv_vpcsum_long* env, int64_t 
                          "recvTcpFrames: negative size", [&](uint64_t* t) {
         return vpcsum_ctx_recv_tcp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
                                           (const vpcsum_desc_t*)desc, (const vpcsum_tcprx_t*)rx, (uint32_t)n, (uint8_t*)dst,
+                                          (uint64_t)dstLen, (uint32_t*)stored, (uint32_t*)out, (uint8_t*)status, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* dst, int64_t dstLen, void* src,
+                                                int64_t srcLen, void* hdr, int32_t nHdr, void* dg, int32_t n,
+                                                void* frameLen, void* out, void* status) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames", n < 0 || nHdr < 0 || dstLen < 0 || srcLen < 0,
+                         "buildUdpFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_build_udp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (uint8_t*)dst, (uint64_t)dstLen, (const uint8_t*)src,
+                                           (uint64_t)srcLen, (const vpcsum_udphdr_t*)hdr, (uint32_t)nHdr,
+                                           (const vpcsum_udpdg_t*)dg, (uint32_t)n, (uint32_t*)frameLen, (uint32_t*)out,
+                                           (uint8_t*)status, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
+                                               void* rx, int32_t n, void* dst, int64_t dstLen, void* stored, void* out,
+                                               void* status) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames", n < 0 || arenaLen < 0 || dstLen < 0,
+                         "recvUdpFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_recv_udp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
+                                          (const vpcsum_desc_t*)desc, (const vpcsum_udprx_t*)rx, (uint32_t)n, (uint8_t*)dst,
                                           (uint64_t)dstLen, (uint32_t*)stored, (uint32_t*)out, (uint8_t*)status, t);
     });
 }

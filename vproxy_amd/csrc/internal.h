@@ -132,6 +132,15 @@ hipError_t launch_tcp_recv(const uint8_t* arena, uint64_t arena_len, const vpcsu
 hipError_t launch_tcp_digest(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, uint32_t n,
                              vpcsum_tcpinfo_t* info, hipStream_t stream);
 
+// UDP datagram build and receive (udp.hip k_udp_build / k_udp_recv, vpcsum.h vpcsum_udp_build_async's and
+// vpcsum_udp_recv_async's rules): the TCP pair's arguments with UDP's records
+hipError_t launch_udp_build(uint8_t* dst, uint64_t dst_len, const uint8_t* src, uint64_t src_len,
+                            const vpcsum_udphdr_t* hdrs, uint32_t n_hdr, const vpcsum_udpdg_t* dgs, uint32_t n,
+                            uint32_t* frame_len_out, uint32_t* out, uint8_t* status, hipStream_t stream);
+hipError_t launch_udp_recv(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const vpcsum_udprx_t* rx,
+                           uint32_t n, uint8_t* dst, uint64_t dst_len, uint32_t* stored, uint32_t* out, uint8_t* status,
+                           hipStream_t stream);
+
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t grid, hipStream_t stream);
 hipError_t launch_pattern_probe(const uint8_t* arena, uint64_t arena_len, const void* desc, uint32_t n, uint32_t* sink,
                                 uint32_t grid, hipStream_t stream);

@@ -26,16 +26,22 @@ static_assert(sizeof(vpcsum_tcprx_t) == 16 && sizeof(vpcsum_tcpinfo_t) == 16, "v
 // and whose L4 offset is one vpcsum_compute_async takes (IPv4: 20..60 in steps of 4 -- the pseudo
 // header is read at bytes 12..19 --, IPv6: at least 40), with a segment of at least 20 bytes.
 // Nothing wraps: l3_off and arena_len - l3_off are compared.
-VPC_TR_FN bool tcp_recv_desc_ok(uint64_t l3_off, uint32_t l3_len, uint32_t l4_off, uint32_t l3_ver, uint32_t l4_proto,
-                                uint32_t flags, uint64_t arena_len) {
-    if (l4_proto != 6u) return false;
+// (l4_recv_desc_ok: the same rule for protocol `proto` with a segment of at least min_seg bytes; the
+// UDP receive, udp_recv.h, asks for 17 and 8.)
+VPC_TR_FN bool l4_recv_desc_ok(uint32_t proto, uint32_t min_seg, uint64_t l3_off, uint32_t l3_len, uint32_t l4_off,
+                               uint32_t l3_ver, uint32_t l4_proto, uint32_t flags, uint64_t arena_len) {
+    if (l4_proto != proto) return false;
     if (l3_ver != 4u && l3_ver != 6u) return false;
     if (!(flags & VPCSUM_F_L4) || (flags & (VPCSUM_F_L4P | VPCSUM_F_RAW | VPCSUM_F_PRE))) return false;
     if ((flags & VPCSUM_F_IP) && l3_ver != 4u) return false;
     if (l4_off > l3_len) return false;
     if (l3_ver == 4u ? (l4_off < 20u || (l4_off & 3u)) : l4_off < 40u) return false;
     if (l3_off > arena_len || (uint64_t)l3_len > arena_len - l3_off) return false;
-    return l3_len - l4_off >= 20u;
+    return l3_len - l4_off >= min_seg;
+}
+VPC_TR_FN bool tcp_recv_desc_ok(uint64_t l3_off, uint32_t l3_len, uint32_t l4_off, uint32_t l3_ver, uint32_t l4_proto,
+                                uint32_t flags, uint64_t arena_len) {
+    return l4_recv_desc_ok(6u, 20u, l3_off, l3_len, l4_off, l3_ver, l4_proto, flags, arena_len);
 }
 
 // The record's own words: no operation but STORE, rsv 0.

@@ -27,40 +27,11 @@
 
 #include "device_common.h"
 #include "internal.h"
+#include "recv_common.h"
 #include "tcp_recv.h"
 #include "team_move.h"
 
 namespace vpcsum {
-
-namespace {
-
-// bytes [p, p + 4) as a little-endian dword, p of any alignment, from the one or two 4-B aligned
-// dwords that hold them
-__device__ __forceinline__ uint32_t load_shifted(uintptr_t p) {
-    const uint32_t sh = (uint32_t)p & 3u;
-    const uintptr_t a = p - sh;
-    const uint32_t lo = *(gu32_t*)a;
-    const uint32_t hi = sh ? *(gu32_t*)(a + 4) : 0u;
-    return alignbyte(hi, lo, sh);
-}
-
-struct Desc {
-    uint64_t l3_off;
-    uint32_t l3_len, l4_off, l3_ver, l4_proto, flags;
-};
-__device__ __forceinline__ Desc load_desc(const vpcsum_desc_t* d) {
-    const u32x4a4_t v = *(gu32x4a4_t*)d;   // 16 B at 8-B alignment
-    Desc r;
-    r.l3_off = ((uint64_t)v.y << 32) | v.x;
-    r.l3_len = v.z & 0xffffu;
-    r.l4_off = v.z >> 16;
-    r.l3_ver = v.w & 0xffu;
-    r.l4_proto = (v.w >> 8) & 0xffu;
-    r.flags = (v.w >> 16) & 0xffu;
-    return r;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void k_tcp_recv(const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                  const vpcsum_desc_t* __restrict__ desc,
@@ -107,36 +78,11 @@ __global__ __launch_bounds__(256) void k_tcp_recv(const uint8_t* __restrict__ ar
     const uint32_t ng = (sp.hi + 15u) >> 4;   // seg_len >= 20: at least two groups' worth of bytes
     const uint64_t acc = move_groups<true>(sp, tl, ng);
 
-    // the pseudo-header's addresses from the L3 header where it lies: 2 (IPv4, bytes 12..19) or 8
-    // (IPv6, bytes 8..39) dwords, a lane each; they start on an even byte of the header, so their sum
-    // is in the segment's own 16-bit word order
-    const bool v4 = d.l3_ver == 4u;
-    uint32_t ph = 0;
-    if (tl < (v4 ? 2u : 8u)) {
-        const uint32_t w = load_shifted(l3 + (v4 ? 12u : 8u) + 4u * tl);
-        ph = (w & 0xffffu) + (w >> 16);
-    }
-    // the IPv4 header sum: lane 7 (it holds no address dword of an IPv4 packet), field masked
+    // the pseudo-header's addresses, a dword per lane, and the IPv4 header sum: lane 7 (it holds no
+    // address dword of an IPv4 packet)
+    uint32_t ph = recv_addr_sum(l3, d.l3_ver, tl);
     uint32_t ipw = 0;
-    if (tl == 7u && (d.flags & VPCSUM_F_IP)) {
-        const uint32_t sh = (uint32_t)l3 & 3u, nw = d.l4_off >> 2;
-        const uintptr_t a = l3 - sh;
-        uint64_t ipacc = 0;
-        uint32_t cur = *(gu32_t*)a, ip_field = 0;
-        for (uint32_t j = 0; j < nw; ++j) {
-            // the next dword: always inside the packet (the segment follows the header)
-            const uint32_t nxt = (sh || j + 1u < nw) ? *(gu32_t*)(a + 4u * j + 4u) : 0u;
-            uint32_t w = alignbyte(nxt, cur, sh);
-            cur = nxt;
-            if (j == 2u) {
-                ip_field = w >> 16;
-                w &= 0xffffu;
-            }
-            ipacc += w;
-        }
-        const uint32_t ipc = 0xffffu - bswap16(fold64(ipacc));
-        ipw = ipc | (bswap16(ip_field) == ipc ? 0x10000u : 0u);
-    }
+    if (tl == 7u && (d.flags & VPCSUM_F_IP)) ipw = recv_ip_header_word(l3, d.l4_off);
 
     uint32_t ps = fold32(team_sum<8>(fold64(acc)));
     if (v0 & 1u) ps = bswap16(ps);   // the one byte parity of the record

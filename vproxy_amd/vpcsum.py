@@ -73,6 +73,15 @@ TCPRX_STORE = 0x01
 # and flags; hlen 0: no record (a refused descriptor), the rest 0
 TCPINFO_DTYPE = np.dtype([("seq", "<u4"), ("ack", "<u4"), ("window", "<u2"), ("data_len", "<u2"), ("hlen", "u1"),
                           ("flags", "u1"), ("rsv", "u1", 2)])
+# vpcsum_udphdr_t is vpcsum_tcphdr_t (TCPHDR_DTYPE) with ack / window / rsv 0.
+# vpcsum_udpdg_t (32 B): one datagram to build -- where its frame goes, where its payload lies,
+# template index, the room at frame_off, payload length (32 bits: too long is refused, not truncated)
+UDPDG_DTYPE = np.dtype([("frame_off", "<u8"), ("data_off", "<u8"), ("hdr", "<u4"), ("frame_cap", "<u4"), ("data_len", "<u4"),
+                        ("rsv", "<u4")])
+# vpcsum_udprx_t (16 B): what the UDP receive does with descriptor i -- where data byte 0 goes in the
+# receive arena, the room there, UDPRX_STORE or 0 (verify only)
+UDPRX_DTYPE = np.dtype([("dst_off", "<u8"), ("dst_cap", "<u4"), ("ops", "u1"), ("rsv", "u1", 3)])
+UDPRX_STORE = 0x01
 
 # Every symbol include/vpcsum.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -111,11 +120,14 @@ EXPORTS = [
     "vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames",
     "Java_io_vproxy_vpcsum_VPCsum_recvTcpFrames",
     "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts", "Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts",
+    "vpcsum_udp_build_async", "vpcsum_udp_recv_async", "vpcsum_ctx_build_udp_frames", "vpcsum_ctx_recv_udp_frames",
+    "Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames", "Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames",
 ]
 
 # additive entry points this binding probes for instead of requiring (see _declare)
 _PROBED = ("vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames",
-           "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts")
+           "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts",
+           "vpcsum_udp_build_async", "vpcsum_udp_recv_async", "vpcsum_ctx_build_udp_frames", "vpcsum_ctx_recv_udp_frames")
 
 
 class VpcsumUnavailable(RuntimeError):
@@ -298,12 +310,16 @@ def _declare(L):
         "vpcsum_ctx_recv_tcp_frames": ([P, P, U64, P, P, U32, P, U64, P, P, P, P], I),
         "vpcsum_tcp_build_bursts_async": ([P, U64, P, U64, P, U32, P, U32, P, U32, U32, P, P, P, P], I),
         "vpcsum_ctx_build_tcp_bursts": ([P, P, U64, P, U64, P, U32, P, U32, P, U32, U32, P, P, P, P], I),
+        "vpcsum_udp_build_async": ([P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
+        "vpcsum_ctx_build_udp_frames": ([P, P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
+        "vpcsum_udp_recv_async": ([P, U64, P, P, U32, P, U64, P, P, P, P], I),
+        "vpcsum_ctx_recv_udp_frames": ([P, P, U64, P, P, U32, P, U64, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
-        # The TCP receive and the TCP send bursts came after ABI version 4 was fixed: a caller probes
-        # for them by looking the symbols up (include/vpcsum.h).  So does this binding -- it loads a
-        # library from before them (tools/ab_libs.sh compares against one), and using tcp_recv() or
-        # tcp_build_bursts() on such a library raises ctypes' "undefined symbol", never a fallback.
+        # The TCP receive, the TCP send bursts and the UDP pair came after ABI version 4 was fixed: a
+        # caller probes for them by looking the symbols up (include/vpcsum.h).  So does this binding -- it
+        # loads a library from before them (tools/ab_libs.sh compares against one), and using tcp_recv(),
+        # tcp_build_bursts() or udp_build() on such a library raises ctypes' "undefined symbol", never a fallback.
         if name in _PROBED and not hasattr(L, name):
             continue
         f = getattr(L, name)
@@ -607,6 +623,35 @@ def tcp_digest(arena, desc, n: int, info, stream=None):
     assert desc.numel() * desc.element_size() >= n * 16 and info.numel() * info.element_size() >= n * TCPINFO_DTYPE.itemsize
     _check(lib().vpcsum_tcp_digest_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(desc), n, _ptr(info),
                                          _stream(stream)), "vpcsum_tcp_digest_async")
+
+
+def udp_build(dst, src, hdrs, n_hdr: int, dgs, n: int, frame_len, out=None, status=None, stream=None):
+    """vpcsum_udp_build_async on device tensors: tcp_build() for datagrams.  `hdrs` n_hdr x 64 bytes
+    (TCPHDR_DTYPE with ack / window / rsv 0), `dgs` n x 32 bytes (UDPDG_DTYPE), `frame_len` n x uint32
+    (written: L, or 0 for a refused record), `out` n x uint32 and `status` n bytes (each may be None).
+    A UDP sum that computes to 0 is stored as 0xffff."""
+    assert hdrs.numel() * hdrs.element_size() >= n_hdr * TCPHDR_DTYPE.itemsize
+    assert dgs.numel() * dgs.element_size() >= n * UDPDG_DTYPE.itemsize
+    assert frame_len.numel() * frame_len.element_size() >= n * 4
+    assert out is None or out.numel() * out.element_size() >= n * 4
+    assert status is None or status.numel() >= n
+    _check(lib().vpcsum_udp_build_async(_ptr(dst), dst.numel() * dst.element_size(), _ptr(src),
+                                        src.numel() * src.element_size(), _ptr(hdrs), n_hdr, _ptr(dgs), n, _ptr(frame_len),
+                                        _ptr(out), _ptr(status), _stream(stream)), "vpcsum_udp_build_async")
+
+
+def udp_recv(arena, desc, rx, n: int, dst, stored, out=None, status=None, stream=None):
+    """vpcsum_udp_recv_async on device tensors: tcp_recv() for datagrams.  `rx` n x 16 bytes
+    (UDPRX_DTYPE); `stored` n x uint32 (written: the segment's bytes past its 8-byte header, 0 for a
+    refused or verify-only record); `out` / `status` (each may be None) what compute() writes with
+    MODE_VERIFY, S_UDP_NOCSUM included.  The bytes are stored whatever the verdict."""
+    assert desc.numel() * desc.element_size() >= n * 16 and rx.numel() * rx.element_size() >= n * UDPRX_DTYPE.itemsize
+    assert stored.numel() * stored.element_size() >= n * 4
+    assert out is None or out.numel() * out.element_size() >= n * 4
+    assert status is None or status.numel() >= n
+    _check(lib().vpcsum_udp_recv_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(desc), _ptr(rx), n, _ptr(dst),
+                                       dst.numel() * dst.element_size(), _ptr(stored), _ptr(out), _ptr(status),
+                                       _stream(stream)), "vpcsum_udp_recv_async")
 
 
 class FlowTable:
@@ -932,6 +977,50 @@ class Context:
                                                 None if out is None else out.ctypes.data,
                                                 None if status is None else status.ctypes.data, ctypes.byref(t)),
                "vpcsum_ctx_recv_tcp_frames")
+        self.wait(t.value)
+        return stored, out, status
+
+    def build_udp_frames(self, dst: np.ndarray, src: np.ndarray, hdrs: np.ndarray, dgs: np.ndarray, want_out: bool = True,
+                         want_status: bool = True):
+        """vpcsum_ctx_build_udp_frames: build_tcp_frames for datagrams -- the frames of `dgs`
+        (UDPDG_DTYPE) built from `hdrs` (TCPHDR_DTYPE with ack / window / rsv 0) and the payloads in
+        `src` into `dst`, which must lie in a registered arena; a registered `src` is read in place,
+        any other staged.  Returns (frame_len, out, status) per record; frame_len 0: refused."""
+        assert hdrs.dtype == TCPHDR_DTYPE and dgs.dtype == UDPDG_DTYPE
+        n, n_hdr = len(dgs), len(hdrs)
+        hd, dg = np.ascontiguousarray(hdrs), np.ascontiguousarray(dgs)
+        frame_len = np.zeros(n, np.uint32)
+        out = np.zeros(n, np.uint32) if want_out else None
+        status = np.zeros(n, np.uint8) if want_status else None
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_build_udp_frames(self.h, dst.ctypes.data, dst.nbytes, src.ctypes.data if src.nbytes else None,
+                                                 src.nbytes, hd.ctypes.data if n_hdr else None, n_hdr,
+                                                 dg.ctypes.data if n else None, n, frame_len.ctypes.data,
+                                                 None if out is None else out.ctypes.data,
+                                                 None if status is None else status.ctypes.data, ctypes.byref(t)),
+               "vpcsum_ctx_build_udp_frames")
+        self.wait(t.value)
+        return frame_len, out, status
+
+    def recv_udp_frames(self, arena: np.ndarray, desc: np.ndarray, rx: np.ndarray, dst: np.ndarray, want_out: bool = True,
+                        want_status: bool = True):
+        """vpcsum_ctx_recv_udp_frames: recv_tcp_frames for datagrams -- descriptor i of `arena`
+        verified and, under rx[i] (UDPRX_DTYPE), its data stored into `dst`, which must lie in a
+        registered arena; a registered `arena` is read in place, any other staged.  Returns
+        (stored, out, status) per record.  Stored whatever the verdict."""
+        assert desc.dtype == DESC_DTYPE and rx.dtype == UDPRX_DTYPE and len(desc) == len(rx)
+        n = len(desc)
+        ds, rr = np.ascontiguousarray(desc), np.ascontiguousarray(rx)
+        stored = np.zeros(n, np.uint32)
+        out = np.zeros(n, np.uint32) if want_out else None
+        status = np.zeros(n, np.uint8) if want_status else None
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_recv_udp_frames(self.h, arena.ctypes.data, arena.nbytes, ds.ctypes.data if n else None,
+                                                rr.ctypes.data if n else None, n, dst.ctypes.data if dst.nbytes else None,
+                                                dst.nbytes, stored.ctypes.data,
+                                                None if out is None else out.ctypes.data,
+                                                None if status is None else status.ctypes.data, ctypes.byref(t)),
+               "vpcsum_ctx_recv_udp_frames")
         self.wait(t.value)
         return stored, out, status
 

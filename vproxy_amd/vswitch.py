@@ -555,6 +555,20 @@ def plan_tcp_store(expecting_seq: int, seq: int, data_len: int):
     return 0, data_len
 
 
+def plan_udp_store(connect, src, sport) -> bool:
+    """What ReceivingQueue.store (UdpListenEntry.java:51-65) decides before it copies a datagram:
+    `connect` is None for an unconnected socket, else its peer as ``(address, port)``; `src` / `sport`
+    are the datagram's source, taken from the parse's tuple.  True: the datagram is enqueued (a
+    UDPRX_STORE record); False: a connected socket drops what is not from its peer, address first,
+    then port (a verify-only record, or none).  The readable() callback stays the host's."""
+    if connect is not None:
+        if src != connect[0]:
+            return False
+        if sport != connect[1]:
+            return False
+    return True
+
+
 def plan_tcp_fetch(ack_seq: int, window: int, mss: int, queue_begin: int, queue_end: int, ack_splits_piece: bool = False):
     """What SendingQueue.fetch() / fetch0() (TcpEntry.java:213-280) return for a sending queue whose
     queued pieces cover [queue_begin, queue_end) without a gap, as one burst: ``(seq, data_len, count)``
