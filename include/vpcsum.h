@@ -53,8 +53,9 @@ extern "C" {
  * the TCP send bursts (vpcsum_tcp_build_bursts_async, vpcsum_ctx_build_tcp_bursts,
  * VPCsum.buildTcpBursts); the UDP datagram build and receive (vpcsum_udp_build_async,
  * vpcsum_udp_recv_async, vpcsum_ctx_build_udp_frames, vpcsum_ctx_recv_udp_frames,
- * VPCsum.buildUdpFrames, VPCsum.recvUdpFrames): new symbols, which a caller probes for by looking
- * them up. */
+ * VPCsum.buildUdpFrames, VPCsum.recvUdpFrames); the ICMP replies (vpcsum_icmp_reply_async,
+ * vpcsum_ctx_reply_icmp_frames, VPCsum.replyIcmpFrames): new symbols, which a caller probes for by
+ * looking them up. */
 #define VPCSUM_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -113,7 +114,8 @@ typedef struct vpcsum_desc {
                                     * after VPCSUM_NAT_SET_TTL when both are set): the packet is
                                     * refused with S_BAD_DESC and nothing is written.  The reference
                                     * never decrements such a packet: IPInputRoute drops it and
-                                    * answers ICMP time exceeded (IPInputRoute.java:81-88)      */
+                                    * answers ICMP time exceeded (IPInputRoute.java:81-88); that
+                                    * answer is vpcsum_icmp_reply_async's VPCSUM_ICMP_TIME_EXCEEDED */
 #define VPCSUM_S_DONE        0x40u /* descriptor processed                                */
 #define VPCSUM_S_BAD_DESC    0x80u /* descriptor rejected (bounds/lengths); nothing written */
 
@@ -692,6 +694,78 @@ int vpcsum_udp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcs
                           const vpcsum_udprx_t* d_rx, uint32_t n, uint8_t* d_dst, uint64_t dst_len,
                           uint32_t* d_stored, uint32_t* d_out, uint8_t* d_status, void* stream);
 
+/* ICMP replies (additive, the ABI version stays 4): the packets the switch generates itself in answer
+ * to a frame the fast path hands back -- the echo reply to a ping of one of its synthetic IPs, port
+ * unreachable for a datagram without a listener, time exceeded for a packet whose TTL / hop limit
+ * would expire (VPCSUM_S_TTL_EXPIRED).  All three end in SwitchUtils.buildEtherIpIcmpPacket
+ * (SwitchUtils.java:202-241); each reply frame is byte-equal to getRawPacket(0) of what it builds.
+ * The source is named by a parse descriptor over the RX arena, as in the receives; the headers are
+ * generated from a 64-byte template, as in the builds; the request's bytes are read once and written
+ * once, summed on the way. */
+#define VPCSUM_ICMP_ECHO_REPLY    1u  /* IcmpInput.respondIcmpPong, IcmpInput.java:100-131            */
+#define VPCSUM_ICMP_PORT_UNREACH  2u  /* IcmpPortUnreachableOutput.handle, :34-78 (from UdpInput :47-50) */
+#define VPCSUM_ICMP_TIME_EXCEEDED 3u  /* IPInputRoute.respondIcmpTimeExceeded, IPInputRoute.java:222-263 */
+
+/* The template carries everything the host decides; the kernel derives no address from the frame.
+ * eth_dst / eth_src: Java's pkb.pkt.getSrc() and the looked-up MAC (or what ip-output-route would
+ * make of them); l2_len 14 or 0; l3_ver; dst: the request's source; src: the request's destination
+ * (echo, port unreachable) or the IP getRoutedSrcIpAndMac picks (time exceeded) -- the host has the
+ * request's addresses from the parse's vpcsum_tuple_t; tos / ttl / ident / frag: the reference uses
+ * 0 / 64 / 0 / 0. */
+typedef vpcsum_tcphdr_t vpcsum_icmphdr_t;   /* bytes 48..57 (ports, ack, window) and rsv must be 0 */
+
+typedef struct vpcsum_icmprp {   /* one per descriptor; 24 bytes, 8-byte aligned */
+    uint64_t frame_off;   /* where the reply starts in the destination arena, any alignment */
+    uint32_t hdr;         /* index into the template array */
+    uint32_t frame_cap;   /* room at frame_off */
+    uint8_t  kind;        /* VPCSUM_ICMP_* */
+    uint8_t  rsv[7];      /* must be 0 */
+} vpcsum_icmprp_t;
+
+/* Descriptor i (as vpcsum_parse_ether_async writes them) pairs with record i.  With seg_len = l3_len -
+ * l4_off and M the ICMP message length, the reply frame of length L = l2_len + (20 | 40) + M at
+ * d_dst + frame_off:
+ *   Ethernet and IP header: exactly as vpcsum_udp_build_async writes them -- IPv4: IHL 5, protocol 1,
+ *     totalLength 20 + M; IPv6: no extension headers, next header 58, payloadLength M.  The reply never
+ *     carries the request's IP options or extension headers.
+ *   Echo reply, M = seg_len: type (0 for IPv4, 129 for IPv6), CODE 0 WHATEVER THE REQUEST'S CODE WAS
+ *     (icmp.setCode(0)), the sum, then request segment bytes [4, seg_len) (inIcmp.getOther()).
+ *   Port unreachable (type 3 code 3, or type 1 code 4) and time exceeded (type 11 or 3, code 0),
+ *     M = 8 + q: type, code, the sum, four zero bytes, then the first q = min(l3_len, l4_off + 64)
+ *     bytes of the IP packet as it lies in the arena (headerLen + 64, headerLen being the rebuilt
+ *     header: IHL * 4 with options, or 40 + extension headers, which is l4_off).  The quoted bytes
+ *     include the TTL as received.
+ *   The ICMP sum: Utils.calculateChecksum over the message with a zero field; ICMPv6 puts the
+ *     pseudo-header of the TEMPLATE's addresses in front.  A computed 0x0000 is stored as it is; a
+ *     message that is all zero stores 0xffff.
+ * A record that is not refused gets d_frame_len[i] = L (required); d_csum[i] (may be NULL) = the
+ * reply's IPv4 header sum in bits 0..15 (0 for IPv6) and its ICMP field in bits 16..31; d_out[i] /
+ * d_status[i] (each may be NULL): for an echo reply exactly what vpcsum_compute_async writes for the
+ * descriptor under VPCSUM_MODE_VERIFY -- THE CALL REPLACES THE VERIFY OF THOSE FRAMES, and the reply
+ * is written whatever the verdict, as in the receives: the caller posts the TX descriptor only on the
+ * verdict its csum-recalc policy accepts --; for the two error kinds 0 and S_DONE.
+ * A record is refused -- d_frame_len[i] 0, d_csum[i] 0, d_out[i] 0, S_BAD_DESC, not one byte written
+ * to d_dst, nothing of the arena read except the one type byte where the rule needs it -- when
+ * hdr >= n_hdr; the template is one vpcsum_udp_build_async refuses or its bytes 48..51 are not 0; its
+ * l3_ver is not the descriptor's; kind is not 1..3; rsv != 0; the descriptor carries F_L4P, F_RAW or
+ * F_PRE, or F_IP on IPv6; l4_off > l3_len, or an l4_off vpcsum_compute_async refuses (IPv4: below 20
+ * or not a multiple of 4; IPv6: below 40); l3_off + l3_len > arena_len (checked without wrapping);
+ * L > frame_cap, or frame_off + L > dst_len (without wrapping); echo: no F_L4, l4_proto not 1 on IPv4
+ * or not 58 on IPv6 (Java drops ICMP of the other family), seg_len < 8, request type not 8 / 128;
+ * port unreachable: l4_proto != 17; time exceeded: an ICMPv6 segment of at least one byte whose type
+ * is 135 or 136 (IPInputRoute.java:64-75 drops NS / NA before the hop check).  Refused means "Java
+ * drops it or the host handles it".
+ * The caller's rules, not checked: error replies go only to frames whose full parse accepted them
+ * (Java runs ensurePartialPacketParsed() first and sends nothing otherwise); reply frames overlap
+ * neither each other nor any request of the batch.  Source and destination may be the same
+ * allocation: an XDP umem holds both rings' chunks.
+ * Alignment (templates, d_frame_len, d_csum and d_out 4-byte, descriptors and records 8-byte), the
+ * limit n <= 2^28 and n == 0 are vpcsum_udp_recv_async's. */
+int vpcsum_icmp_reply_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc,
+                            const vpcsum_icmphdr_t* d_hdr, uint32_t n_hdr, const vpcsum_icmprp_t* d_rp, uint32_t n,
+                            uint8_t* d_dst, uint64_t dst_len, uint32_t* d_frame_len,
+                            uint32_t* d_csum, uint32_t* d_out, uint8_t* d_status, void* stream);
+
 /* Streaming-read ceiling probe: reads `bytes` from d_buf with 16-B lanes, writes one word per
  * block into d_sink.  Used by bench.py to report a measured HBM read roof next to 8 TB/s. */
 int vpcsum_read_probe_async(const uint8_t* d_buf, uint64_t bytes, uint32_t* d_sink,
@@ -909,6 +983,20 @@ int vpcsum_ctx_recv_udp_frames(vpcsum_ctx_t* ctx, const uint8_t* h_arena, uint64
                                const vpcsum_desc_t* h_desc, const vpcsum_udprx_t* h_rx, uint32_t n,
                                uint8_t* h_dst, uint64_t dst_len, uint32_t* h_stored, uint32_t* h_out,
                                uint8_t* h_status, uint64_t* ticket);
+/* vpcsum_icmp_reply_async from host memory, in one submission: the source by
+ * vpcsum_ctx_recv_udp_frames' plan -- a registered h_arena (the RX umem) is read in place, any other
+ * is staged exactly as vpcsum_ctx_submit stages it --, the destination by
+ * vpcsum_ctx_build_udp_frames' -- h_dst must be inside a REGISTERED arena (an unregistered
+ * destination is refused); it may be the arena h_arena lies in.  n and n_hdr are each at most the
+ * context's max_pkts.  At vpcsum_ctx_wait h_frame_len[i] (required), h_csum[i], h_out[i] and
+ * h_status[i] (each may be NULL) hold what vpcsum_icmp_reply_async writes, and the replies are in
+ * h_dst whatever an echo's verdict.  Always launched: no service-grid, device-group or process-wide
+ * form. */
+int vpcsum_ctx_reply_icmp_frames(vpcsum_ctx_t* ctx, const uint8_t* h_arena, uint64_t arena_len,
+                                 const vpcsum_desc_t* h_desc, const vpcsum_icmphdr_t* h_hdr, uint32_t n_hdr,
+                                 const vpcsum_icmprp_t* h_rp, uint32_t n, uint8_t* h_dst, uint64_t dst_len,
+                                 uint32_t* h_frame_len, uint32_t* h_csum, uint32_t* h_out, uint8_t* h_status,
+                                 uint64_t* ticket);
 /* The egress flush of a batch holding NAT'd frames: vpcsum_ctx_submit where
  * descriptors with VPCSUM_F_PRE take their L4 sum from h_pre[i] (pre_fmt as vpcsum_pre_async;
  * entries of other descriptors are ignored) and the others are summed in full, in one submission.
@@ -1106,6 +1194,13 @@ int Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames(PNIEnv_vpcsum_long* env, int64_t
 int Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
                                                void* rx, int32_t n, void* dst, int64_t dstLen, void* stored, void* out,
                                                void* status);
+/* VPCsum.replyIcmpFrames(long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment hdr,
+ *                        int nHdr, MemorySegment rp, int n, MemorySegment dst, long dstLen, MemorySegment frameLen,
+ *                        MemorySegment csum, MemorySegment out, MemorySegment status)
+ *   -> long ticket (vpcsum_ctx_reply_icmp_frames) */
+int Java_io_vproxy_vpcsum_VPCsum_replyIcmpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
+                                                 void* hdr, int32_t nHdr, void* rp, int32_t n, void* dst, int64_t dstLen,
+                                                 void* frameLen, void* csum, void* out, void* status);
 /* VPCsum.setService(long ctx, int idleUs) */
 int Java_io_vproxy_vpcsum_VPCsum_setService(PNIEnv_vpcsum_void* env, int64_t ctx, int32_t idleUs);
 /* VPCsum.waitFor(long ctx, long ticket) */

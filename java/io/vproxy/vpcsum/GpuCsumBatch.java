@@ -487,6 +487,25 @@ public final class GpuCsumBatch implements AutoCloseable {
     }
 
     /**
+     * The ICMP packets the switch answers a received batch with (IcmpInput.respondIcmpPong,
+     * IcmpPortUnreachableOutput.handle, IPInputRoute.respondIcmpTimeExceeded), built on the GPU
+     * straight into TX chunks of the umem: {@code count} frames described in {@code frameDesc} (the
+     * parse's descriptors), one record each in {@code rp} ({@link VPCsum#icmpRp}) over {@code nHdr}
+     * templates.  Fills {@code frameLenOut} (u32 per record): the reply's length for the TX descriptor,
+     * or 0 -- the record was refused: Java drops that packet or the host answers it.  For an echo
+     * {@code statusOut} holds the request's verify verdict (the call replaces {@link #verify} for it)
+     * and the reply is written whatever the verdict: post it only on the verdict the csum-recalc
+     * policy accepts.  Needs a library with the entry ({@code VPCsumLib.hasIcmpReply()}).
+     */
+    public MemorySegment replyIcmp(MemorySegment frameDesc, MemorySegment hdr, int nHdr, MemorySegment rp, int count,
+                                   MemorySegment frameLenOut, MemorySegment statusOut) throws IOException {
+        long t = VPCsum.get().replyIcmpFrames(env, ctx, umem, umemLen, frameDesc, hdr, nHdr, rp, count, umem, umemLen, frameLenOut,
+            MemorySegment.NULL, MemorySegment.NULL, statusOut);
+        VPCsum.get().waitFor(env, ctx, t);
+        return frameLenOut;
+    }
+
+    /**
      * Ingress verify of {@code count} frames already described in {@code desc} (e.g. built by the
      * GPU parser, vpcsum_parse_ether_async): fills {@code status} (S_IP_OK / S_L4_OK /
      * S_UDP_NOCSUM per frame) without touching the frames.  The returned segment is this

@@ -258,6 +258,26 @@ public class VPCsum {
         rx.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 12, store ? UDPRX_STORE : 0);   // ops, rsv[3] 0
     }
 
+    /** bytes of one vpcsum_icmprp_t reply record ({@link #icmpRp}) */
+    public static final int ICMP_RP = 24;
+    /** vpcsum_icmprp_t.kind: IcmpInput.respondIcmpPong / IcmpPortUnreachableOutput.handle /
+     * IPInputRoute.respondIcmpTimeExceeded */
+    public static final int ICMP_ECHO_REPLY = 1, ICMP_PORT_UNREACH = 2, ICMP_TIME_EXCEEDED = 3;
+
+    /** Fill the 24-byte record at {@code rp[off..]} for the ICMP reply to one received frame: the
+     * reply goes to {@code frameOff} of the destination arena (room {@code frameCap} there, a TX chunk),
+     * {@code hdrIndex} names the template ({@link #tcpHdr} with ports, ack and window 0: eth_dst the
+     * request's pkb.pkt.getSrc(), eth_src the looked-up MAC, dst the request's source, src the
+     * request's destination -- for time exceeded the IP getRoutedSrcIpAndMac picks --, ttl 64),
+     * {@code kind} one of ICMP_*. */
+    public static void icmpRp(MemorySegment rp, long off, long frameOff, int hdrIndex, int frameCap, int kind) {
+        final var LE = java.nio.ByteOrder.LITTLE_ENDIAN;
+        rp.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off, frameOff);
+        rp.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 8, hdrIndex);
+        rp.set(java.lang.foreign.ValueLayout.JAVA_INT_UNALIGNED.withOrder(LE), off + 12, frameCap);
+        rp.set(java.lang.foreign.ValueLayout.JAVA_LONG_UNALIGNED.withOrder(LE), off + 16, (long) (kind & 0xff));   // kind, rsv[7] 0
+    }
+
     /** Fields of the 16-byte digest at {@code info[off..]} (vpcsum_tcp_digest_async): seq and ack as
      * TcpPacket.getSeqNum / getAckNum return them (unsigned, in a long), window, payload length,
      * header length (0: no record, the descriptor was refused) and flags. */
@@ -868,6 +888,48 @@ public class VPCsum {
         int ERR;
         try {
             ERR = (int) MH.invokeExact(ENV.MEMORY, ctx, arena, arenaLen, desc, rx, n, dst, dstLen, stored, out, status);
+        } catch (Throwable THROWABLE) {
+            throw PanamaUtils.convertInvokeExactException(THROWABLE);
+        }
+        if (ERR != 0) {
+            ENV.throwIf(java.io.IOException.class);
+            ENV.throwLast();
+        }
+        return ENV.returnLong();
+    }
+
+    /* The ICMP replies: resolved on first use, as the UDP pair is (VPCsumLib.hasIcmpReply). */
+    private static volatile MethodHandle replyIcmpFramesMH;
+
+    /** The ICMP replies (vpcsum_ctx_reply_icmp_frames): for descriptor i of {@code arena} (the RX
+     * umem, read in place when registered) the reply that record i of {@link #ICMP_RP} bytes
+     * ({@link #icmpRp}) names -- echo reply, port unreachable, time exceeded -- written as a finished
+     * Ethernet / IP / ICMP frame into {@code dst}, a registered arena (the same umem's TX chunks, or
+     * another).  After {@link #waitFor}: frameLen[i] (u32) is the frame's length, 0 for a refused record
+     * (Java drops that packet, or the host answers it); csum[i] (u32, may be NULL) the reply's sums;
+     * for an echo status[i] / out[i] (each may be NULL) are the REQUEST's verify verdict -- the call
+     * replaces the verify of those frames, and THE REPLY IS WRITTEN WHATEVER THE VERDICT: post the TX
+     * descriptor only on the verdict the csum-recalc policy accepts; for the two errors S_DONE / 0. */
+    public long replyIcmpFrames(PNIEnv ENV, long ctx, MemorySegment arena, long arenaLen, MemorySegment desc, MemorySegment hdr,
+                                int nHdr, MemorySegment rp, int n, MemorySegment dst, long dstLen, MemorySegment frameLen,
+                                MemorySegment csum, MemorySegment out, MemorySegment status) throws java.io.IOException {
+        MethodHandle MH = replyIcmpFramesMH;
+        if (MH == null) {
+            if (!VPCsumLib.hasIcmpReply()) {
+                throw new java.io.IOException("libvpcsum has no replyIcmpFrames: the library is older than this binding");
+            }
+            MH = PanamaUtils.lookupPNIFunction(new PNILinkOptions().setCritical(false),
+                "Java_io_vproxy_vpcsum_VPCsum_replyIcmpFrames", long.class /* ctx */, MemorySegment.class /* arena */,
+                long.class /* arenaLen */, MemorySegment.class /* desc */, MemorySegment.class /* hdr */, int.class /* nHdr */,
+                MemorySegment.class /* rp */, int.class /* n */, MemorySegment.class /* dst */, long.class /* dstLen */,
+                MemorySegment.class /* frameLen */, MemorySegment.class /* csum */, MemorySegment.class /* out */,
+                MemorySegment.class /* status */);
+            replyIcmpFramesMH = MH;
+        }
+        ENV.reset();
+        int ERR;
+        try {
+            ERR = (int) MH.invokeExact(ENV.MEMORY, ctx, arena, arenaLen, desc, hdr, nHdr, rp, n, dst, dstLen, frameLen, csum, out, status);
         } catch (Throwable THROWABLE) {
             throw PanamaUtils.convertInvokeExactException(THROWABLE);
         }

@@ -62,6 +62,11 @@ final class VPCsumLib {
         return has("Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames") && has("Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames");
     }
 
+    /** The ICMP replies ({@link VPCsum#replyIcmpFrames}, {@link GpuCsumBatch#replyIcmp}). */
+    static boolean hasIcmpReply() {
+        return has("Java_io_vproxy_vpcsum_VPCsum_replyIcmpFrames");
+    }
+
     /** IOException unless the loaded library speaks ABI {@code expected} (VPCsum.ABI_VERSION). */
     static void requireAbi(int expected) throws IOException {
         int v = abiVersion();

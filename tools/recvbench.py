@@ -15,7 +15,11 @@ Algorithmic bytes per frame: the segment read + data_len written + descriptor an
 timing, r's receive buffer is compared with b's and with the send buffer, r's status and out with a's.
 With --udp only the UDP leg runs: vpcsum_udp_recv_async (k_udp_recv) on datagrams of 1,360 and 1,472
 payload bytes, timed against leg r on segments of the same payload and against leg c, in the same run.
-Prints one JSON line.  usage: recvbench.py [frames] [--launches N] [--udp]"""
+With --icmp-echo only the echo leg runs: vpcsum_icmp_reply_async (k_icmp_reply) answering IPv4 echo
+requests whose ICMP messages are 1,360 and 1,472 bytes into a second arena of the same layout (leg e)
+and into chunks with 6 more bytes of headroom (leg s), timed
+against k_udp_recv with STORE on UDP frames of the same segment lengths and against leg c.
+Prints one JSON line.  usage: recvbench.py [frames] [--launches N] [--udp | --icmp-echo]"""
 import ctypes
 import json
 import os
@@ -31,6 +35,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 1 << 17
 launches = int(sys.argv[sys.argv.index("--launches") + 1]) if "--launches" in sys.argv else 50
 rounds = 3
 STRIDE, HEADROOM, HLEN = 2048, 384, 54
+SHIFT = 6   # --icmp-echo leg s: the replies' chunks have 6 more bytes of headroom than the requests'
 
 V.lib()
 hip = None
@@ -126,8 +131,113 @@ def udp_leg():
     print(json.dumps(r_all))
 
 
+def icmp_echo_leg():
+    """--icmp-echo: vpcsum_icmp_reply_async (k_icmp_reply) on IPv4 echo requests whose ICMP messages are
+    1,360 and 1,472 bytes, answered into a second arena of the same layout, against k_udp_recv with
+    STORE on UDP frames of the same segment lengths and a contiguous copy of the same bytes, in the
+    same run.  Leg e writes each reply at its request's own offset in the chunk (source and the reply's
+    16-B grid agree, every group is one aligned load); leg s writes it SHIFT bytes further on, a TX chunk
+    of another headroom (source and grid differ modulo 4, as they do for the receive's back-to-back
+    runs).  The requests are laid out on the device (a header row and random bodies), their sums
+    written by vpcsum_compute_async with MODE_WRITE; before timing every request must verify, and the
+    replies -- parsed and verified in turn -- must carry the requests' bytes from 4 on."""
+    uh = hdr.copy()
+    uh["ack"], uh["window"] = 0, 0
+    d_uh = dev(uh)
+    ih = uh.copy()
+    ih["sport"], ih["dport"] = 0, 0
+    ih["src"][0, :4], ih["dst"][0, :4] = (10, 0, 0, 2), (10, 0, 0, 1)
+    d_ih = dev(ih)
+    r_all = {"frames_per_batch": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,
+             "shifted_reply_at": HEADROOM + SHIFT,
+             "frames": "Ethernet / IPv4 / ICMP echo requests against Ethernet / IPv4 / UDP of the same segment length"}
+    off = np.arange(n, dtype=np.uint64)
+    foff = dev((off * STRIDE + HEADROOM).copy())
+    for M in (1360, 1472):
+        g = torch.Generator(device="cuda").manual_seed(M)
+        # the requests: 02bb.. -> 02aa.., 10.0.0.1 -> 10.0.0.2, type 8 code 0, sums 0 until MODE_WRITE fills them
+        row = bytes.fromhex("02aa0000000102bb000000020800") + bytes([0x45, 0]) + (20 + M).to_bytes(2, "big") + bytes.fromhex("00004000") + \
+            bytes([64, 1, 0, 0, 10, 0, 0, 1, 10, 0, 0, 2]) + bytes([8, 0, 0, 0])
+        req = torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda")
+        r2 = req.view(n, STRIDE)
+        r2[:, HEADROOM:HEADROOM + len(row)] = dev(np.frombuffer(row, np.uint8))
+        r2[:, HEADROOM + len(row):HEADROOM + 34 + M] = torch.randint(0, 256, (n, M - 4), dtype=torch.uint8, device="cuda", generator=g)
+        flen_q = torch.full((n,), 34 + M, dtype=torch.int32, device="cuda")
+        desc_q = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+        V.parse_ether(req, foff, flen_q, n, desc_q)
+        V.compute(req, desc_q, n, None, None, V.MODE_WRITE)
+        rp = np.zeros(n, V.ICMPRP_DTYPE)
+        rp["frame_off"], rp["frame_cap"], rp["kind"] = off * STRIDE + HEADROOM, STRIDE - HEADROOM, V.ICMP_ECHO_REPLY
+        d_rp = dev(rp)
+        rp["frame_off"], rp["frame_cap"] = off * STRIDE + HEADROOM + SHIFT, STRIDE - HEADROOM - SHIFT
+        d_rp_s = dev(rp)
+        rep, rep_s = (torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda") for _ in range(2))
+        flen_e, cs_e, out_e = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3))
+        st_e = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        # the UDP twin: datagrams whose segment is M bytes, stored back to back
+        data_len = M - 8
+        dg = np.zeros(n, V.UDPDG_DTYPE)
+        dg["frame_off"], dg["data_off"], dg["frame_cap"], dg["data_len"] = off * STRIDE + HEADROOM, off * data_len, STRIDE - HEADROOM, data_len
+        sent = torch.randint(0, 256, (n * data_len,), dtype=torch.uint8, device="cuda", generator=g)
+        fr_u = torch.zeros(n * STRIDE, dtype=torch.uint8, device="cuda")
+        flen_u = torch.zeros(n, dtype=torch.int32, device="cuda")
+        V.udp_build(fr_u, sent, d_uh, 1, dev(dg), n, flen_u, None, None)
+        desc_u = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+        V.parse_ether(fr_u, foff, flen_u, n, desc_u)
+        urx = np.zeros(n, V.UDPRX_DTYPE)
+        urx["dst_off"], urx["dst_cap"], urx["ops"] = off * data_len, data_len, V.UDPRX_STORE
+        d_urx = dev(urx)
+        rb_u, copy = (torch.zeros(n * data_len, dtype=torch.uint8, device="cuda") for _ in range(2))
+        stored, out_u = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+        st_u = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        legs = {"e_icmp_echo": lambda: V.icmp_reply(req, desc_q, d_ih, 1, d_rp, n, rep, flen_e, cs_e, out_e, st_e),
+                "s_icmp_echo_shifted": lambda: V.icmp_reply(req, desc_q, d_ih, 1, d_rp_s, n, rep_s, flen_e, cs_e, out_e, st_e),
+                "u_udp_recv": lambda: V.udp_recv(fr_u, desc_u, d_urx, n, rb_u, stored, out_u, st_u),
+                "c_contiguous_copy": lambda: copy.copy_(sent)}
+        legs["s_icmp_echo_shifted"]()
+        legs["e_icmp_echo"]()
+        legs["u_udp_recv"]()
+        torch.cuda.synchronize()
+        ok = V.S_DONE | V.S_IP_OK | V.S_L4_OK
+        assert int((st_e != ok).sum().item()) == 0 and int((flen_e != 34 + M).sum().item()) == 0, "every request verifies and is answered"
+        assert int((st_u != ok).sum().item()) == 0 and torch.equal(rb_u, sent)
+        p2 = rep.view(n, STRIDE)
+        assert torch.equal(p2[:, HEADROOM + 38:HEADROOM + 34 + M], r2[:, HEADROOM + 38:HEADROOM + 34 + M]), "the replies carry the requests' bytes"
+        assert int(p2[:, HEADROOM + 34:HEADROOM + 36].sum().item()) == 0 and int(p2[:, :HEADROOM].sum().item()) == 0
+        assert torch.equal(rep_s.view(n, STRIDE)[:, HEADROOM + SHIFT:HEADROOM + SHIFT + 34 + M], p2[:, HEADROOM:HEADROOM + 34 + M]), \
+            "the shifted replies are the same frames"
+        desc_p = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+        st_p = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        V.parse_ether(rep, foff, flen_e, n, desc_p)
+        V.compute(rep, desc_p, n, None, st_p, V.MODE_VERIFY)
+        torch.cuda.synchronize()
+        assert int((st_p != ok).sum().item()) == 0, "every reply verifies"
+        us = {k: [] for k in legs}
+        for _ in range(rounds):
+            for k, fn in legs.items():
+                us[k].append(round(timed(fn), 2))
+        # bytes moved per frame: the segment read once; the echo writes the frame (34 + M), the receive M - 8
+        r = {"icmp_msg_len": M, "echo_frame_len": 34 + M, "udp_frame_len": 34 + M, "echo_bytes_per_frame": M + 34 + M + 64,
+             "udp_bytes_per_frame": M + M - 8}
+        for k, v in us.items():
+            r[k] = {"us_rounds": v, "us_median": sorted(v)[len(v) // 2]}
+        r["s_over_u"] = round(r["s_icmp_echo_shifted"]["us_median"] / r["u_udp_recv"]["us_median"], 4)
+        r["s_over_e"] = round(r["s_icmp_echo_shifted"]["us_median"] / r["e_icmp_echo"]["us_median"], 4)
+        r["e_over_u"] = round(r["e_icmp_echo"]["us_median"] / r["u_udp_recv"]["us_median"], 4)
+        r["byte_ratio"] = round(r["echo_bytes_per_frame"] / r["udp_bytes_per_frame"], 4)
+        r["e_over_c"] = round(r["e_icmp_echo"]["us_median"] / r["c_contiguous_copy"]["us_median"], 3)
+        r["e_round_spread"] = round(max(us["e_icmp_echo"]) / min(us["e_icmp_echo"]) - 1, 4)
+        r["u_round_spread"] = round(max(us["u_udp_recv"]) / min(us["u_udp_recv"]) - 1, 4)
+        r_all[f"msg_len_{M}"] = r
+        del req, rep, rep_s, sent, fr_u, rb_u, copy, r2, p2
+    print(json.dumps(r_all))
+
+
 if "--udp" in sys.argv:
     udp_leg()
+    sys.exit(0)
+if "--icmp-echo" in sys.argv:
+    icmp_echo_leg()
     sys.exit(0)
 
 res = {"frames_per_batch": n, "launches": launches, "rounds": rounds, "stride": STRIDE, "frame_at": HEADROOM,

@@ -144,7 +144,8 @@ def main(tag):
         if d:
             json.dump({"src_hash": prov["src_hash"], "head": prov["head"], **d},
                       open(os.path.join(P, f"{tag}_{out}.json"), "w"), indent=1)
-    for f in sorted(glob.glob(os.path.join(G, f"{tag}_udp_*bench_*.log"))):   # tools/segbench.py / recvbench.py --udp, one log per process
+    # tools/segbench.py / recvbench.py --udp and recvbench.py --icmp-echo, one log per process
+    for f in sorted(glob.glob(os.path.join(G, f"{tag}_udp_*bench_*.log")) + glob.glob(os.path.join(G, f"{tag}_icmp_*bench_*.log"))):
         d = json_line(f)
         if d:
             json.dump({"src_hash": prov["src_hash"], "head": prov["head"], **d},

@@ -10,9 +10,9 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvpcsum.so")
-SOURCES = ["kernels.hip", "nat.hip", "flow.hip", "tcp_build.hip", "tcp_burst.hip", "tcp_recv.hip", "udp.hip", "api.cpp"]
+SOURCES = ["kernels.hip", "nat.hip", "flow.hip", "tcp_build.hip", "tcp_burst.hip", "tcp_recv.hip", "udp.hip", "icmp.hip", "api.cpp"]
 HEADERS = ["internal.h", "launch_modes.h", "batch_plan.h", "device_common.h", "pre_common.h", "tcp_rewrite.h", "flow_table.h",
-           "tcp_build.h", "tcp_burst.h", "tcp_frame.h", "tcp_recv.h", "team_move.h", "recv_common.h", "udp_build.h", "udp_recv.h",
+           "tcp_build.h", "tcp_burst.h", "tcp_frame.h", "tcp_recv.h", "team_move.h", "recv_common.h", "udp_build.h", "udp_recv.h", "icmp_reply.h",
            os.path.join("..", "..", "include", "vpcsum.h")]
 ARCH = os.environ.get("VPCSUM_ARCH", "gfx950")
 

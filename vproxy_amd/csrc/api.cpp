@@ -28,6 +28,7 @@
 #include "tcp_build.h"
 #include "tcp_burst.h"
 #include "tcp_recv.h"
+#include "icmp_reply.h"
 #include "udp_build.h"
 #include "udp_recv.h"
 #include "vpcsum.h"
@@ -153,8 +154,9 @@ struct DeviceOnly : Owned<T, hipFree> {
 
 // One copy of a finished batch's results into a buffer of the caller's.
 struct HandBack { void* dst; const void* src; size_t bytes; };
-// The most any entry hands back: the status bytes and two more arrays (say descriptors and tuples)
-constexpr size_t kHandBackMax = 3;
+// The most any entry hands back: the status bytes and three more arrays (the ICMP replies: frame
+// lengths, the replies' sums, the requests' verdict words)
+constexpr size_t kHandBackMax = 4;
 
 // What a staged batch scatters into the caller's frames when it is finished.
 enum class Scatter { None, NatHeaders, CsumFields };
@@ -202,8 +204,8 @@ struct Slot {
     DeviceOnly<vpcsum_tuple_t> d_tu;   // a flow batch's tuples (parse -> lookup)
     Mapped<uint8_t> h_verdict;         // and its verdicts
     DeviceOnly<vpcsum_fastpath_t> d_fp;   // a forwarding flow batch's Fastpath records (lookup -> L2 write)
-    Mapped<uint32_t> h_port;           // and its output ports
-    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records (a UDP build batch's: the same 32 B), templates and frame lengths
+    Mapped<uint32_t> h_port;           // and its output ports (an ICMP reply batch's d_csum words)
+    Mapped<vpcsum_tcpseg_t> h_tseg;    // a TCP build batch's records (a UDP build batch's: the same 32 B; an ICMP reply batch's: 24 B), templates and frame lengths
     Mapped<vpcsum_tcphdr_t> h_thdr;
     Mapped<uint32_t> h_tlen;           // (a TCP receive batch's stored counts too)
     Mapped<vpcsum_tcprx_t> h_trx;      // a TCP receive batch's records (a UDP receive batch's: the same 16 B)
@@ -1731,6 +1733,50 @@ static int ctx_recv_frames(vpcsum_ctx_t* c, const char* what, const char* launch
     });
 }
 
+// The ICMP replies of host memory (vpcsum_ctx_reply_icmp_frames): the source by ctx_recv_frames' plan
+// (read in place from a registered arena, else staged as vpcsum_ctx_submit stages it), the destination
+// by ctx_build_frames' (written in place, registered).  The 24-B records lie in the slot's pinned
+// build-record buffer (h_tseg, 32 B per packet), the templates in h_thdr, the frame lengths in h_tlen
+// and the replies' sums in h_port.
+static int ctx_reply_icmp(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc,
+                          const vpcsum_icmphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_icmprp_t* h_rp, uint32_t n, uint8_t* h_dst,
+                          uint64_t dst_len, uint32_t* h_frame_len, uint32_t* h_csum, uint32_t* h_out, uint8_t* h_status,
+                          uint64_t* ticket) {
+    static_assert(sizeof(vpcsum_icmprp_t) <= sizeof(vpcsum_tcpseg_t) && alignof(vpcsum_icmprp_t) <= alignof(vpcsum_tcpseg_t),
+                  "the records fit the build-record buffer");
+    const char* what = "vpcsum_ctx_reply_icmp_frames";
+    if (desc_args(c, what, "arena, descriptors or records", h_arena, h_desc, h_rp, n, ticket) != 0) return -1;
+    if (n_hdr > c->max_pkts) return fail("%s: %u templates > capacity %u", what, n_hdr, c->max_pkts);
+    if (n && (!h_dst || !h_frame_len || (!h_hdr && n_hdr))) return fail("%s: NULL destination, templates or frame lengths", what);
+    return desc_entry(c, const_cast<uint8_t*>(h_arena), arena_len, h_desc, n, VPCSUM_MODE_VERIFY,
+                      [&](Slot& s, Batch& b, const BatchSpan& sp, uint8_t* base) {
+        uint8_t* dst_dev = n ? mapped_dev(c, h_dst, dst_len) : nullptr;
+        if (n && !dst_dev) return fail("%s: the destination must be registered (vpcsum_ctx_register_arena)", what);
+        b.user_arena = nullptr;   // nothing goes back into the requests
+        b.user_desc = nullptr;
+        b.zero_copy = true;       // the replies are written in place through the destination's mapping
+        if (n) {
+            if (slot_scratch(c, what, s.h_tseg, s.h_thdr, s.h_tlen, s.h_port) != 0) return -1;
+            b.hand_back({status_of(c, s, false, h_status, n), {h_frame_len, s.h_tlen.p, (size_t)n * 4},
+                         {h_csum, s.h_port.p, (size_t)n * 4}, out_of(c, s, false, h_out, n)});
+            memcpy(s.h_tseg.p, h_rp, (size_t)n * sizeof(vpcsum_icmprp_t));
+            if (n_hdr) memcpy(s.h_thdr.p, h_hdr, (size_t)n_hdr * sizeof(vpcsum_icmphdr_t));
+            uint64_t dev_len = arena_len;
+            if (base) {
+                memcpy(s.h_desc.p, h_desc, (size_t)n * sizeof(vpcsum_desc_t));
+            } else {
+                if (stage_desc_frames(c, s, what, h_arena, arena_len, h_desc, n, sp, &dev_len) != 0) return -1;
+                if (stage_frames_up(s, dev_len) != 0) return -1;
+            }
+            VPC_CHECK(launch_icmp_reply(base ? base : s.d_arena.p, dev_len, s.h_desc.dev, s.h_thdr.dev, n_hdr,
+                                        reinterpret_cast<const vpcsum_icmprp_t*>(s.h_tseg.dev), n, dst_dev, dst_len, s.h_tlen.dev,
+                                        h_csum ? s.h_port.dev : nullptr, h_out ? s.h_out.dev : nullptr, s.h_status.dev, s.stream),
+                      "ICMP reply launch");
+        }
+        return slot_commit(s, b, ticket);
+    });
+}
+
 extern "C" {
 
 int vpcsum_flowtab_create(int device, uint32_t max_flows, vpcsum_flowtab_t** out) {
@@ -1990,6 +2036,28 @@ int vpcsum_udp_recv_async(const uint8_t* d_arena, uint64_t arena_len, const vpcs
     } VPC_CATCH("vpcsum_udp_recv_async")
 }
 
+int vpcsum_icmp_reply_async(const uint8_t* d_arena, uint64_t arena_len, const vpcsum_desc_t* d_desc, const vpcsum_icmphdr_t* d_hdr,
+                            uint32_t n_hdr, const vpcsum_icmprp_t* d_rp, uint32_t n, uint8_t* d_dst, uint64_t dst_len,
+                            uint32_t* d_frame_len, uint32_t* d_csum, uint32_t* d_out, uint8_t* d_status, void* stream) {
+    try {
+        if (n == 0) return 0;
+        if (!d_arena && arena_len) return fail("vpcsum_icmp_reply_async: NULL arena");
+        if (!d_desc || !d_rp) return fail("vpcsum_icmp_reply_async: NULL descriptors or records");
+        if (!d_hdr && n_hdr) return fail("vpcsum_icmp_reply_async: NULL templates");
+        if (!d_dst) return fail("vpcsum_icmp_reply_async: NULL destination arena");
+        if (!d_frame_len) return fail("vpcsum_icmp_reply_async: NULL frame lengths");
+        if (((uintptr_t)d_desc | (uintptr_t)d_rp) & 7) return fail("vpcsum_icmp_reply_async: descriptors or records not 8-byte aligned");
+        if ((uintptr_t)d_hdr & 3) return fail("vpcsum_icmp_reply_async: templates not 4-byte aligned");
+        if ((uintptr_t)d_frame_len & 3) return fail("vpcsum_icmp_reply_async: frame lengths not 4-byte aligned");
+        if (((uintptr_t)d_csum | (uintptr_t)d_out) & 3) return fail("vpcsum_icmp_reply_async: sum or out words not 4-byte aligned");
+        if (n > (1u << 28)) return fail("vpcsum_icmp_reply_async: %u records > 2^28", n);
+        VPC_CHECK(launch_icmp_reply(d_arena, arena_len, d_desc, d_hdr, n_hdr, d_rp, n, d_dst, dst_len, d_frame_len, d_csum, d_out,
+                                    d_status, (hipStream_t)stream),
+                  "ICMP reply launch");
+        return 0;
+    } VPC_CATCH("vpcsum_icmp_reply_async")
+}
+
 int vpcsum_flowtab_collect(vpcsum_flowtab_t* f, uint64_t* h_cookies, uint32_t cap, uint32_t* n_out, void* stream) {
     try {
         if (!f || !n_out) return fail("vpcsum_flowtab_collect: NULL table or count");
@@ -2158,6 +2226,16 @@ int vpcsum_ctx_recv_udp_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t
         return ctx_recv_frames(c, "vpcsum_ctx_recv_udp_frames", "UDP receive launch", h_arena, arena_len, h_desc, h_rx, n, h_dst,
                                dst_len, h_stored, h_out, h_status, ticket, launch_udp_recv);
     } VPC_CATCH("vpcsum_ctx_recv_udp_frames")
+}
+
+int vpcsum_ctx_reply_icmp_frames(vpcsum_ctx_t* c, const uint8_t* h_arena, uint64_t arena_len, const vpcsum_desc_t* h_desc,
+                                 const vpcsum_icmphdr_t* h_hdr, uint32_t n_hdr, const vpcsum_icmprp_t* h_rp, uint32_t n,
+                                 uint8_t* h_dst, uint64_t dst_len, uint32_t* h_frame_len, uint32_t* h_csum, uint32_t* h_out,
+                                 uint8_t* h_status, uint64_t* ticket) {
+    try {
+        return ctx_reply_icmp(c, h_arena, arena_len, h_desc, h_hdr, n_hdr, h_rp, n, h_dst, dst_len, h_frame_len, h_csum, h_out,
+                              h_status, ticket);
+    } VPC_CATCH("vpcsum_ctx_reply_icmp_frames")
 }
 
 int vpcsum_ctx_pipeline(vpcsum_ctx_t* c, uint8_t* h_arena, uint32_t stride, uint32_t copy_bytes,
@@ -2874,6 +2952,18 @@ int Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames(PNIEnv_vpcsum_long* env, int64_t 
         return vpcsum_ctx_recv_udp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
                                           (const vpcsum_desc_t*)desc, (const vpcsum_udprx_t*)rx, (uint32_t)n, (uint8_t*)dst,
                                           (uint64_t)dstLen, (uint32_t*)stored, (uint32_t*)out, (uint8_t*)status, t);
+    });
+}
+
+int Java_io_vproxy_vpcsum_VPCsum_replyIcmpFrames(PNIEnv_vpcsum_long* env, int64_t ctx, void* arena, int64_t arenaLen, void* desc,
+                                                 void* hdr, int32_t nHdr, void* rp, int32_t n, void* dst, int64_t dstLen,
+                                                 void* frameLen, void* csum, void* out, void* status) {
+    return pni_returning(env, "Java_io_vproxy_vpcsum_VPCsum_replyIcmpFrames", n < 0 || nHdr < 0 || arenaLen < 0 || dstLen < 0,
+                         "replyIcmpFrames: negative size", [&](uint64_t* t) {
+        return vpcsum_ctx_reply_icmp_frames((vpcsum_ctx_t*)(intptr_t)ctx, (const uint8_t*)arena, (uint64_t)arenaLen,
+                                            (const vpcsum_desc_t*)desc, (const vpcsum_icmphdr_t*)hdr, (uint32_t)nHdr,
+                                            (const vpcsum_icmprp_t*)rp, (uint32_t)n, (uint8_t*)dst, (uint64_t)dstLen,
+                                            (uint32_t*)frameLen, (uint32_t*)csum, (uint32_t*)out, (uint8_t*)status, t);
     });
 }
 

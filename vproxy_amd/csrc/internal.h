@@ -141,6 +141,13 @@ hipError_t launch_udp_recv(const uint8_t* arena, uint64_t arena_len, const vpcsu
                            uint32_t n, uint8_t* dst, uint64_t dst_len, uint32_t* stored, uint32_t* out, uint8_t* status,
                            hipStream_t stream);
 
+// ICMP replies (icmp.hip k_icmp_reply, vpcsum.h vpcsum_icmp_reply_async's rule): descriptor i answered
+// under rps[i] from template hdrs[rps[i].hdr], the frame written at dst + rps[i].frame_off;
+// frame_len_out[i] = L or 0 for a refused record; csum_out / out / status may be NULL
+hipError_t launch_icmp_reply(const uint8_t* arena, uint64_t arena_len, const vpcsum_desc_t* desc, const vpcsum_icmphdr_t* hdrs,
+                             uint32_t n_hdr, const vpcsum_icmprp_t* rps, uint32_t n, uint8_t* dst, uint64_t dst_len,
+                             uint32_t* frame_len_out, uint32_t* csum_out, uint32_t* out, uint8_t* status, hipStream_t stream);
+
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t grid, hipStream_t stream);
 hipError_t launch_pattern_probe(const uint8_t* arena, uint64_t arena_len, const void* desc, uint32_t n, uint32_t* sink,
                                 uint32_t grid, hipStream_t stream);

@@ -82,6 +82,11 @@ UDPDG_DTYPE = np.dtype([("frame_off", "<u8"), ("data_off", "<u8"), ("hdr", "<u4"
 # receive arena, the room there, UDPRX_STORE or 0 (verify only)
 UDPRX_DTYPE = np.dtype([("dst_off", "<u8"), ("dst_cap", "<u4"), ("ops", "u1"), ("rsv", "u1", 3)])
 UDPRX_STORE = 0x01
+# vpcsum_icmphdr_t is vpcsum_tcphdr_t (TCPHDR_DTYPE) with ports / ack / window / rsv 0.
+# vpcsum_icmprp_t (24 B): the ICMP reply to descriptor i -- where the reply frame goes, template index,
+# the room at frame_off, ICMP_ECHO_REPLY / ICMP_PORT_UNREACH / ICMP_TIME_EXCEEDED
+ICMPRP_DTYPE = np.dtype([("frame_off", "<u8"), ("hdr", "<u4"), ("frame_cap", "<u4"), ("kind", "u1"), ("rsv", "u1", 7)])
+ICMP_ECHO_REPLY, ICMP_PORT_UNREACH, ICMP_TIME_EXCEEDED = 1, 2, 3
 
 # Every symbol include/vpcsum.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -122,12 +127,14 @@ EXPORTS = [
     "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts", "Java_io_vproxy_vpcsum_VPCsum_buildTcpBursts",
     "vpcsum_udp_build_async", "vpcsum_udp_recv_async", "vpcsum_ctx_build_udp_frames", "vpcsum_ctx_recv_udp_frames",
     "Java_io_vproxy_vpcsum_VPCsum_buildUdpFrames", "Java_io_vproxy_vpcsum_VPCsum_recvUdpFrames",
+    "vpcsum_icmp_reply_async", "vpcsum_ctx_reply_icmp_frames", "Java_io_vproxy_vpcsum_VPCsum_replyIcmpFrames",
 ]
 
 # additive entry points this binding probes for instead of requiring (see _declare)
 _PROBED = ("vpcsum_tcp_recv_async", "vpcsum_tcp_digest_async", "vpcsum_ctx_recv_tcp_frames",
            "vpcsum_tcp_build_bursts_async", "vpcsum_ctx_build_tcp_bursts",
-           "vpcsum_udp_build_async", "vpcsum_udp_recv_async", "vpcsum_ctx_build_udp_frames", "vpcsum_ctx_recv_udp_frames")
+           "vpcsum_udp_build_async", "vpcsum_udp_recv_async", "vpcsum_ctx_build_udp_frames", "vpcsum_ctx_recv_udp_frames",
+           "vpcsum_icmp_reply_async", "vpcsum_ctx_reply_icmp_frames")
 
 
 class VpcsumUnavailable(RuntimeError):
@@ -314,9 +321,11 @@ def _declare(L):
         "vpcsum_ctx_build_udp_frames": ([P, P, U64, P, U64, P, U32, P, U32, P, P, P, P], I),
         "vpcsum_udp_recv_async": ([P, U64, P, P, U32, P, U64, P, P, P, P], I),
         "vpcsum_ctx_recv_udp_frames": ([P, P, U64, P, P, U32, P, U64, P, P, P, P], I),
+        "vpcsum_icmp_reply_async": ([P, U64, P, P, U32, P, U32, P, U64, P, P, P, P, P], I),
+        "vpcsum_ctx_reply_icmp_frames": ([P, P, U64, P, P, U32, P, U32, P, U64, P, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
-        # The TCP receive, the TCP send bursts and the UDP pair came after ABI version 4 was fixed: a
+        # The TCP receive, the TCP send bursts, the UDP pair and the ICMP replies came after ABI version 4 was fixed: a
         # caller probes for them by looking the symbols up (include/vpcsum.h).  So does this binding -- it
         # loads a library from before them (tools/ab_libs.sh compares against one), and using tcp_recv(),
         # tcp_build_bursts() or udp_build() on such a library raises ctypes' "undefined symbol", never a fallback.
@@ -652,6 +661,25 @@ def udp_recv(arena, desc, rx, n: int, dst, stored, out=None, status=None, stream
     _check(lib().vpcsum_udp_recv_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(desc), _ptr(rx), n, _ptr(dst),
                                        dst.numel() * dst.element_size(), _ptr(stored), _ptr(out), _ptr(status),
                                        _stream(stream)), "vpcsum_udp_recv_async")
+
+
+def icmp_reply(arena, desc, hdrs, n_hdr: int, rps, n: int, dst, frame_len, csum=None, out=None, status=None, stream=None):
+    """vpcsum_icmp_reply_async on device tensors: the ICMP reply to each descriptor of `arena` -- echo
+    reply, port unreachable or time exceeded, as rps[i].kind says -- written into `dst` as a finished
+    Ethernet / IP / ICMP frame.  `hdrs` n_hdr x 64 bytes (TCPHDR_DTYPE with ports / ack / window / rsv
+    0), `rps` n x 24 bytes (ICMPRP_DTYPE), `frame_len` n x uint32 (written: L, or 0 for a refused
+    record), `csum` n x uint32 (the reply's sums), `out` n x uint32 and `status` n bytes (an echo: what
+    compute() writes for the request with MODE_VERIFY; an error: 0 and S_DONE); each of the last three
+    may be None.  `dst` may be `arena`.  An echo reply is written whatever the request's verdict."""
+    assert desc.numel() * desc.element_size() >= n * 16 and rps.numel() * rps.element_size() >= n * ICMPRP_DTYPE.itemsize
+    assert hdrs.numel() * hdrs.element_size() >= n_hdr * TCPHDR_DTYPE.itemsize
+    assert frame_len.numel() * frame_len.element_size() >= n * 4
+    assert csum is None or csum.numel() * csum.element_size() >= n * 4
+    assert out is None or out.numel() * out.element_size() >= n * 4
+    assert status is None or status.numel() >= n
+    _check(lib().vpcsum_icmp_reply_async(_ptr(arena), arena.numel() * arena.element_size(), _ptr(desc), _ptr(hdrs), n_hdr,
+                                         _ptr(rps), n, _ptr(dst), dst.numel() * dst.element_size(), _ptr(frame_len),
+                                         _ptr(csum), _ptr(out), _ptr(status), _stream(stream)), "vpcsum_icmp_reply_async")
 
 
 class FlowTable:
@@ -1023,6 +1051,31 @@ class Context:
                "vpcsum_ctx_recv_udp_frames")
         self.wait(t.value)
         return stored, out, status
+
+    def reply_icmp_frames(self, arena: np.ndarray, desc: np.ndarray, hdrs: np.ndarray, rps: np.ndarray, dst: np.ndarray,
+                          want_csum: bool = True, want_out: bool = True, want_status: bool = True):
+        """vpcsum_ctx_reply_icmp_frames: the ICMP reply to descriptor i of `arena` under rps[i]
+        (ICMPRP_DTYPE) and its template of `hdrs` (TCPHDR_DTYPE with ports / ack / window / rsv 0),
+        written into `dst`, which must lie in a registered arena (it may be the one `arena` lies in);
+        a registered `arena` is read in place, any other staged.  Returns (frame_len, csum, out,
+        status) per record; frame_len 0: refused."""
+        assert desc.dtype == DESC_DTYPE and rps.dtype == ICMPRP_DTYPE and hdrs.dtype == TCPHDR_DTYPE and len(desc) == len(rps)
+        n, n_hdr = len(desc), len(hdrs)
+        ds, rr, hd = np.ascontiguousarray(desc), np.ascontiguousarray(rps), np.ascontiguousarray(hdrs)
+        frame_len = np.zeros(n, np.uint32)
+        csum = np.zeros(n, np.uint32) if want_csum else None
+        out = np.zeros(n, np.uint32) if want_out else None
+        status = np.zeros(n, np.uint8) if want_status else None
+        t = ctypes.c_uint64()
+        _check(lib().vpcsum_ctx_reply_icmp_frames(self.h, arena.ctypes.data, arena.nbytes, ds.ctypes.data if n else None,
+                                                  hd.ctypes.data if n_hdr else None, n_hdr, rr.ctypes.data if n else None, n,
+                                                  dst.ctypes.data if dst.nbytes else None, dst.nbytes, frame_len.ctypes.data,
+                                                  None if csum is None else csum.ctypes.data,
+                                                  None if out is None else out.ctypes.data,
+                                                  None if status is None else status.ctypes.data, ctypes.byref(t)),
+               "vpcsum_ctx_reply_icmp_frames")
+        self.wait(t.value)
+        return frame_len, csum, out, status
 
     def set_service(self, idle_us: int):
         """Low-latency flushes from registered arenas (persistent service grid); 0 = off."""

@@ -569,6 +569,38 @@ def plan_udp_store(connect, src, sport) -> bool:
     return True
 
 
+def plan_icmp_replies(status: np.ndarray, desc: np.ndarray, udp_listen_miss: np.ndarray, local: np.ndarray):
+    """The frames of a batch that the reference answers with an ICMP packet of its own, as
+    ``(indices, kinds)`` -- what a caller turns into ICMPRP_DTYPE records for V.icmp_reply /
+    Context.reply_icmp_frames, one template per frame from its tuple.  `status` is the batch's status
+    after the NAT (the parse's S_BAD_DESC, the NAT's S_TTL_EXPIRED), `desc` its parse descriptors.
+
+    * S_TTL_EXPIRED: IPInputRoute.route answers time exceeded instead of decrementing
+      (IPInputRoute.java:81-88) -- ICMP_TIME_EXCEEDED.  The kernel refuses the NS / NA that route()
+      drops before the hop check.
+    * `udp_listen_miss[i]`: the caller's lookupUdpListen found no socket for a UDP datagram to a local
+      address (UdpInput.java:47-50 -> IcmpPortUnreachableOutput) -- ICMP_PORT_UNREACH.
+    * `local[i]`: the caller's lookup says the destination is one of the switch's synthetic IPs and the packet
+      is ICMP of its own family with a checksum to verify (IcmpInput.java:40-63) -- an echo candidate,
+      ICMP_ECHO_REPLY; the kernel checks the type (8 / 128) and refuses everything else, which Java
+      drops or hands to NDP.
+
+    A frame the parse refused gets nothing; a frame with an expired TTL gets time exceeded only (the
+    route node runs before the L4 inputs).  Error replies go only to frames whose FULL parse accepted
+    them: Java runs ensurePartialPacketParsed() first, and so must the caller."""
+    n = len(status)
+    assert len(desc) == n and len(udp_listen_miss) == n and len(local) == n
+    ttl = (status & V.S_TTL_EXPIRED) != 0
+    parsed = ((status & V.S_BAD_DESC) == 0) & ~ttl
+    ver, proto = desc["l3_ver"], desc["l4_proto"]
+    unreach = parsed & np.asarray(udp_listen_miss, bool) & (proto == 17)
+    echo = parsed & np.asarray(local, bool) & ((desc["flags"] & V.F_L4) != 0) & \
+        (((ver == 4) & (proto == 1)) | ((ver == 6) & (proto == 58)))
+    kinds = np.where(ttl, V.ICMP_TIME_EXCEEDED, np.where(unreach, V.ICMP_PORT_UNREACH, np.where(echo, V.ICMP_ECHO_REPLY, 0)))
+    idx = np.flatnonzero(kinds)
+    return idx.astype(np.int64), kinds[idx].astype(np.uint8)
+
+
 def plan_tcp_fetch(ack_seq: int, window: int, mss: int, queue_begin: int, queue_end: int, ack_splits_piece: bool = False):
     """What SendingQueue.fetch() / fetch0() (TcpEntry.java:213-280) return for a sending queue whose
     queued pieces cover [queue_begin, queue_end) without a gap, as one burst: ``(seq, data_len, count)``
